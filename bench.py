@@ -15,6 +15,14 @@ top-radix-bits shard of the library's C ABI (srs_shard_*,
 csrc/srs_shard.hip, through ctypes): histogram all-reduce, partition,
 grouped send/recv over RCCL/xGMI, local sort. Weak scaling.
 
+A plain run sets up, warms up, times the steps and prints the headline
+figures (Gkeys/s, ms_per_step, the roofline from the timed steps' own scatter
+markers, the pass model). --full adds everything else the line can report,
+each from runs of its own after the timed steps: per-kernel times, the
+allocator variants, the full-size verification, the CPU baselines and the
+extra configs C2 and C3. --dump-outputs DIR writes the last timed step's
+output arrays (a fixed sample of them at this size) as DIR/<name>.npy.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -51,6 +59,16 @@ def parse():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--n", type=float, default=1e9, help="keys per GPU")
     ap.add_argument("--config", default="c1", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything else the line "
+                         "can report: per-kernel times, the steps with and without event "
+                         "markers, the allocator variants, the full-size verification, the CPU "
+                         "baselines, the 'extra' configs and the shard line's T(1); without it a "
+                         "run sets up, warms up, times the steps and prints the headline figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (the "
+                         "sorted key and payload arrays, or a fixed seeded sample of them) as "
+                         "DIR/<name>.npy")
     ap.add_argument("--cpu-sample", type=float, default=1e9,
                     help="keys of the headline config's CPU baseline (the reference on one "
                          "host core; 1e9 = the config itself; 0 = skip)")
@@ -97,7 +115,10 @@ def parse():
     argv = sys.argv[1:]
     if argv[:1] == ["--"]:  # the launcher's separator (launcher_cmd)
         argv = argv[1:]
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 DISTS = ("uniform", "gaussian", "zero", "zeroone", "sorted", "reverse", "almostsorted",
@@ -366,17 +387,18 @@ def main():
         dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
     dev = torch.device("cuda", local_rank)
 
-    res = measure(args.config, args, torch, srs_amd, dist, dev, rank, world, shard)
+    res = measure(args.config, args, torch, srs_amd, dist, dev, rank, world, shard,
+                  dump_dir=args.dump_outputs)
 
     cpu = None
-    if rank == 0 and args.cpu_sample > 0 and (world == 1):
+    if args.full and rank == 0 and args.cpu_sample > 0 and (world == 1):
         try:
             cpu = cpu_baseline(args.config, min(args.cpu_sample, args.n), args.cpu_warmup)
         except Exception as e:  # report, never hide
             cpu = {"error": repr(e)}
 
     extra = {}
-    if world == 1 and not shard and args.config == "c1" and args.dist == "uniform":
+    if args.full and world == 1 and not shard and args.config == "c1" and args.dist == "uniform":
         for name in [e for e in args.extra.split(",") if e and e != "none"]:
             torch.cuda.empty_cache()
             try:
@@ -400,9 +422,10 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": res["ms_per_step"],
-            "ms_per_step_without_event_markers": res["ms_per_step_without_event_markers"],
-            "ms_per_step_with_all_event_markers": res["ms_per_step_with_all_event_markers"],
-            **{k: res[k] for k in ("ms_per_step_plain_alloc", "ms_per_step_inplace",
+            "full": args.full,
+            **{k: res[k] for k in ("ms_per_step_without_event_markers",
+                                   "ms_per_step_with_all_event_markers",
+                                   "ms_per_step_plain_alloc", "ms_per_step_inplace",
                                    "alloc_variants") if k in res},
             "higher_is_better": True,
             "scaling": "weak",
@@ -412,10 +435,11 @@ def main():
             "config": res["config"],
             "roofline": res["roofline"],
             "pass_model": res["pass_model"],
-            "kernels": res["kernels"],
-            "cpu_baseline": cpu,
-            "verified": res["verified"],
         }
+        if args.full:
+            out.update(kernels=res["kernels"], cpu_baseline=cpu, verified=res["verified"])
+        if res.get("dumped") is not None:
+            out["dumped"] = res["dumped"]
         if res.get("phases") is not None:
             out["phases"] = res["phases"]
         if extra:
@@ -425,11 +449,51 @@ def main():
         dist.destroy_process_group()
 
 
-def measure(cfg_name, args, torch, srs_amd, dist, dev, rank, world, shard):
+def dump_outputs(dump_dir, cols, rank, world, torch):
+    """Writes the output arrays `cols` ({name: 1-d device array}, all of one
+    length) of the last timed step to dump_dir/<name>.npy. More than 2^20
+    records: the records at a fixed, seeded sample of 2^20 positions (first
+    and last among them), whose positions go to sample_index.npy. Values keep
+    every bit: float32 keys as float32, 4-byte integers as float64, 8-byte
+    integers as a float64 (m, 2) array of their (high, low) 32-bit halves.
+    At most 2^20 * (8 + 16 + 16) bytes = 40 MiB. Returns the file names."""
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    sfx = "" if world == 1 else f"_rank{rank}"
+    n = next(iter(cols.values())).numel()
+    m = 1 << 20
+    if n > m:
+        pos = np.random.default_rng(20240607).choice(n, size=m - 2, replace=False)
+        pos = np.unique(np.concatenate([pos, [0, n - 1]])).astype(np.int64)
+    else:
+        pos = np.arange(n, dtype=np.int64)
+    idx = torch.from_numpy(pos).to(next(iter(cols.values())).device)
+    arrays = {"sample_index": pos.astype(np.float64)}
+    for name, t in cols.items():
+        h = t[idx].cpu().numpy()
+        if h.dtype == np.float32:
+            a = h
+        elif h.dtype.itemsize == 4:
+            a = h.view(np.uint32).astype(np.float64)
+        else:
+            u = h.view(np.uint64)
+            a = np.stack([(u >> np.uint64(32)).astype(np.float64),
+                          (u & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=1)
+        arrays[name] = a
+    files = []
+    for name, a in arrays.items():
+        np.save(os.path.join(dump_dir, f"{name}{sfx}.npy"), a)
+        files.append(f"{name}{sfx}.npy")
+    return files
+
+
+def measure(cfg_name, args, torch, srs_amd, dist, dev, rank, world, shard, dump_dir=None):
     """Generates the config's resident input, runs W warmup + K timed steps
     (barrier + synchronize on both sides, max over ranks) and returns the
     config's numbers: Gkeys/s, roofline of the dominant kernel (HIP events
-    on the sort's stream), pass-model bytes and the full-size verification."""
+    on the sort's stream) and pass-model bytes; with --full also the
+    per-kernel times of further steps, the allocator variants and the
+    full-size verification. dump_dir: see dump_outputs."""
     kname, psizes, layout, cdesc = CONFIGS[cfg_name]
     kind = kind_id(kname)
     n = int(args.n)
@@ -535,26 +599,41 @@ def measure(cfg_name, args, torch, srs_amd, dist, dev, rank, world, shard):
     srs_amd.set_kernel_timing(False)
     elapsed = t1 - t0
     timed = collect()
-    # The per-kernel breakdown comes from a few more steps with markers
-    # around every launch (they cost a step 0.05-0.2 ms), and the same
-    # steps without any markers are timed for comparison.
+    dumped = None
+    if dump_dir is not None:
+        # what the last timed step left in the arrays its caller receives
+        if shard:
+            cols = {"keys": shard_out[0][0],
+                    **{f"payload{c}": p for c, p in enumerate(shard_out[0][1])}}
+        elif layout == "aos":
+            cols = {"records_key": rec_out[:, 0], "records_payload": rec_out[:, 1]}
+        else:
+            cols = {"keys": keys_out, **{f"payload{c}": p for c, p in enumerate(pays_out)}}
+        dumped = dump_outputs(dump_dir, cols, rank, world, torch)
+    full = args.full
+    # --full: the per-kernel breakdown comes from a few more steps with
+    # markers around every launch (they cost a step 0.05-0.2 ms), and the
+    # same steps without any markers are timed for comparison.
     nb = min(args.steps, 5)
-    srs_amd.reset_kernel_stats()
-    srs_amd.set_kernel_timing(True)
-    sync()
-    t2 = time.perf_counter()
-    for _ in range(nb):
-        step()
-    sync()
-    ms_all_events = (time.perf_counter() - t2) / nb * 1e3
-    srs_amd.set_kernel_timing(False)
-    kstats = collect()
-    sync()
-    t2 = time.perf_counter()
-    for _ in range(nb):
-        step()
-    sync()
-    ms_no_events = (time.perf_counter() - t2) / nb * 1e3
+    kstats = timed
+    ms_all_events = ms_no_events = None
+    if full:
+        srs_amd.reset_kernel_stats()
+        srs_amd.set_kernel_timing(True)
+        sync()
+        t2 = time.perf_counter()
+        for _ in range(nb):
+            step()
+        sync()
+        ms_all_events = (time.perf_counter() - t2) / nb * 1e3
+        srs_amd.set_kernel_timing(False)
+        kstats = collect()
+        sync()
+        t2 = time.perf_counter()
+        for _ in range(nb):
+            step()
+        sync()
+        ms_no_events = (time.perf_counter() - t2) / nb * 1e3
     phases = None
     if shard:
         # per-rank phase stamps of the last step (HIP events, from the
@@ -569,10 +648,10 @@ def measure(cfg_name, args, torch, srs_amd, dist, dev, rank, world, shard):
                 "stamps_ms": rep["stamps_ms"],
                 "bytes_to_peer_per_round": rep["bytes_to_peer_per_round"],
                 **shard_mod.link_figures(rep)}
-        if world == 1:
+        if world == 1 and (full or args.t1_ms is not None):
             # the head and tail measured here, in DESIGN.md §7's 8-GPU model
             # against T(1) = the plain one-GPU sort of the same input in the
-            # same process (or --t1-ms)
+            # same process (--full) or --t1-ms
             t1 = args.t1_ms
             if t1 is None:
                 t1 = plain_step_ms(keys, pays, kind, args.steps, torch, srs_amd)
@@ -584,7 +663,7 @@ def measure(cfg_name, args, torch, srs_amd, dist, dev, rank, world, shard):
         dist.all_gather_object(allph, mine)
         phases = allph
     alloc_ms = {}
-    if not shard and args.alloc_steps > 0:
+    if full and not shard and args.alloc_steps > 0:
         alloc_ms = alloc_variants(args, step_args=(keys, pays, rec, kind, layout), torch=torch,
                                   srs_amd=srs_amd)
     if shard:
@@ -620,7 +699,7 @@ def measure(cfg_name, args, torch, srs_amd, dist, dev, rank, world, shard):
     L_g = min(math.ceil(math.log(max(n / 4096, 1.0001), 256)), ks)
     b_alg = n * (L_g * (c_b + 2 * s_b) + 2 * s_b)
     pass_model_gbs = b_alg * world / (elapsed / args.steps) / 1e9
-    levels_run = (kstats.get("count", {}).get("launches", 0) / nb) if not shard else None
+    levels_run = (kstats.get("count", {}).get("launches", 0) / nb) if full and not shard else None
     pass_model = {"B_alg_bytes_per_gpu": b_alg, "L_g": L_g, "gbs": round(pass_model_gbs, 1),
                   "frac_of_8TBs": round(pass_model_gbs / world / HBM_PEAK_GBS, 4)}
     if levels_run:
@@ -631,9 +710,11 @@ def measure(cfg_name, args, torch, srs_amd, dist, dev, rank, world, shard):
             b_run / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4)
 
     if rank == 0:
-        progress(f"{cfg_name}: {ms_per_step:.3f} ms per step; verifying")
+        progress(f"{cfg_name}: {ms_per_step:.3f} ms per step" + ("; verifying" if full else ""))
     verified = None
-    if not args.no_verify and not shard:
+    if not full:
+        pass
+    elif not args.no_verify and not shard:
         if layout == "aos":
             verified = verify(None, None, rec_out, kname, psizes, torch,
                               ins=(rec[:, 0], [rec[:, 1]]),
@@ -651,8 +732,8 @@ def measure(cfg_name, args, torch, srs_amd, dist, dev, rank, world, shard):
         "value": round(gkeys, 4),
         "unit": "Gkeys/s",
         "ms_per_step": round(ms_per_step, 3),
-        "ms_per_step_without_event_markers": round(ms_no_events, 3),
-        "ms_per_step_with_all_event_markers": round(ms_all_events, 3),
+        **({"ms_per_step_without_event_markers": round(ms_no_events, 3),
+            "ms_per_step_with_all_event_markers": round(ms_all_events, 3)} if full else {}),
         "dtype": kname if kname != "u64" else "uint64",
         "config": {"workload": cfg_name + ": " + cdesc +
                    ("" if args.dist == "uniform" or cfg_name != args.config
@@ -665,8 +746,9 @@ def measure(cfg_name, args, torch, srs_amd, dist, dev, rank, world, shard):
         "pass_model": pass_model,
         "kernels": {k: {"launches": v["launches"], "avg_ms": round(v["ms"] / v["launches"], 4),
                         "total_ms_per_step": round(v["ms"] / nb, 3)}
-                    for k, v in kstats.items()},
+                    for k, v in kstats.items()} if full else None,
         "verified": verified,
+        "dumped": dumped,
         **alloc_ms,
         **({"phases": phases} if phases is not None else {}),
     }

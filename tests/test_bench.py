@@ -147,3 +147,78 @@ def test_verify_shards_over_gloo():
     good, bad = res[1], res[2]
     assert all(good.values()), good
     assert not bad["multiset_hash_equal"], bad
+
+
+def _u64_of_halves(a):
+    import numpy as np
+    return (a[:, 0].astype(np.uint64) << np.uint64(32)) | a[:, 1].astype(np.uint64)
+
+
+def test_dump_outputs_sample_is_fixed_and_lossless(tmp_path):
+    """--dump-outputs' writer on host arrays: above 2^20 records a sample at
+    positions that do not change from call to call (first and last among
+    them), every bit of every column recoverable, within 64 MB."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    g = torch.Generator()
+    g.manual_seed(9)
+    n = (1 << 20) + 4321
+    k = torch.randint(-2**63, 2**63 - 1, (n,), dtype=torch.int64, generator=g)
+    p = torch.randint(-2**31, 2**31 - 1, (n,), dtype=torch.int32, generator=g)
+    f = torch.randn(n, generator=g)
+    cols = {"keys": k, "payload0": p, "payload1": f}
+    names = bench.dump_outputs(str(tmp_path / "a"), cols, 0, 1, torch)
+    bench.dump_outputs(str(tmp_path / "b"), cols, 0, 1, torch)
+    assert sorted(names) == ["keys.npy", "payload0.npy", "payload1.npy", "sample_index.npy"]
+    a = {x[:-4]: np.load(tmp_path / "a" / x) for x in names}
+    for x in names:
+        assert np.array_equal(a[x[:-4]], np.load(tmp_path / "b" / x))
+        assert a[x[:-4]].dtype in (np.float32, np.float64)
+    pos = a["sample_index"].astype(np.int64)
+    assert pos[0] == 0 and pos[-1] == n - 1 and np.all(np.diff(pos) > 0) and len(pos) <= 1 << 20
+    assert np.array_equal(_u64_of_halves(a["keys"]), k.numpy().view(np.uint64)[pos])
+    assert np.array_equal(a["payload0"], p.numpy().view(np.uint32)[pos].astype(np.float64))
+    assert np.array_equal(a["payload1"], f.numpy()[pos])
+    assert sum(os.path.getsize(tmp_path / "a" / x) for x in names) <= 64 * 1000 * 1000
+    # at most 2^20 records: all of them; N > 1 ranks: one file set per rank
+    small = bench.dump_outputs(str(tmp_path / "c"), {"keys": k[:1000]}, 1, 2, torch)
+    assert sorted(small) == ["keys_rank1.npy", "sample_index_rank1.npy"]
+    assert np.array_equal(_u64_of_halves(np.load(tmp_path / "c" / "keys_rank1.npy")),
+                          k[:1000].numpy().view(np.uint64))
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_sorted_output(tmp_path):
+    """A plain run (no --full) prints the headline figures only, times exactly
+    --steps steps, and --dump-outputs holds the sorted output of the last
+    timed step: keys in order at the sampled positions, payload = f(key)."""
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+    n = 3_000_001
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--n", str(n), "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, env=_env(), timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = r.stdout.strip().splitlines()
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["unit"] == "Gkeys/s" and d["higher_is_better"] is True and d["dtype"] == "uint64"
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["full"] is False
+    assert d["ms_per_step"] > 0
+    assert abs(d["value"] - n / (d["ms_per_step"] * 1e-3) / 1e9) <= 0.01 * d["value"] + 1e-3
+    for k in ("kernels", "cpu_baseline", "verified", "extra", "alloc_variants",
+              "ms_per_step_without_event_markers"):
+        assert k not in d, k
+    assert sorted(d["dumped"]) == ["keys.npy", "payload0.npy", "sample_index.npy"]
+    pos = np.load(tmp_path / "sample_index.npy").astype(np.int64)
+    keys = _u64_of_halves(np.load(tmp_path / "keys.npy"))
+    pay = _u64_of_halves(np.load(tmp_path / "payload0.npy"))
+    assert pos[0] == 0 and pos[-1] == n - 1 and len(keys) == len(pos) == len(pay)
+    assert np.all(keys[1:] >= keys[:-1])
+    assert np.array_equal(pay, bench._sm64(keys, np))
+    # the first and last records are the input's extremes (the device fill's generator)
+    kin, _ = bench.host_workload("c1", n, 42 << 32)
+    assert keys[0] == kin.min() and keys[-1] == kin.max()

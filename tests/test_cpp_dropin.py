@@ -109,7 +109,9 @@ def test_dropin_accepts_the_reference_call_forms():
      "same type"),
     ("radix_sort::sort<true, radix_sort::BitSorterSIMD, MySorter>(16, 4, k)",
      "user-defined leaf sorter"),
-])
+], ids=["bramas_float_key", "bramas_descending", "bramas_mixed_payload", "user_defined_leaf_sorter"])
+# (explicit ids: the C++ calls hold "::", pytest's own separator of module,
+# class and test in a node id, which tools that split ids there misread)
 def test_dropin_rejects_what_the_reference_rejects(call, msg):
     src = ('#include "simd_sort/radix_sort.hpp"\n'
            "using namespace simd_sort; struct MySorter {};\n"

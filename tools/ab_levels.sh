@@ -7,7 +7,7 @@ mkdir -p gpurun_out/ab
 for r in $(seq ${REPS:-2}); do for c in ${CFGS:-c2}; do for v in $VARS; do
   log=gpurun_out/ab/${c}_${v}_$r.json
   SRS_AMD_LIB=$PWD/simd-radix-sort_amd/lib/variants/$v/libsrs_amd.so timeout -k 10 200 \
-    python bench.py --config $c --steps ${STEPS:-10} --extra none --cpu-sample 0 $EXTRA > $log 2> ${log%.json}.err
+    python bench.py --full --config $c --steps ${STEPS:-10} --extra none --cpu-sample 0 $EXTRA > $log 2> ${log%.json}.err
   rc=$?; [ $rc -ne 0 ] && { echo "$c $v rc=$rc"; tail -3 ${log%.json}.err; exit $rc; }
   python3 - "$log" "$c" "$v" <<'PY'
 import json, sys

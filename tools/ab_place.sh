@@ -9,9 +9,9 @@ for i in $(seq 1 $N); do
   for arm in placed plain; do
     log=gpurun_out/abp/${arm}_$i.log
     if [ $arm = plain ]; then
-      SRS_PLACE=0 timeout -k 10 300 python bench.py --steps ${STEPS:-10} --cpu-sample 0 --extra none --out-alloc torch > $log 2>&1
+      SRS_PLACE=0 timeout -k 10 300 python bench.py --full --steps ${STEPS:-10} --cpu-sample 0 --extra none --out-alloc torch > $log 2>&1
     else
-      timeout -k 10 300 python bench.py --steps ${STEPS:-10} --cpu-sample 0 --extra none > $log 2>&1
+      timeout -k 10 300 python bench.py --full --steps ${STEPS:-10} --cpu-sample 0 --extra none > $log 2>&1
     fi
     rc=$?
     [ $rc -ne 0 ] && { echo "$arm $i rc=$rc"; tail -5 $log; exit $rc; }

@@ -16,7 +16,7 @@
 #   lat          tools/latency.py over the small / mid sizes
 #   latab        tools/latency.py at 1M-4M keys without / with the mid-level launch
 #   phases       tools/latency_phases.py (kernel time per family), without / with the mid-level launch
-#   bench        the default bench.py line (what the driver runs)
+#   bench        the default bench.py --full line (every figure the bench reports)
 # After a crash, abort or time limit (rc >= 124, 134, 139) nothing else runs.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/${1:?usage: gpu_run.sh <out> step...}
@@ -45,13 +45,13 @@ for s in "$@"; do
     f:*) step "pytest_${s#f:}" 600 $PT "tests/${s#f:}.py" ;;
     exitcheck) step exitcheck 300 rocprofv3 --kernel-trace -d "$OUT/exitcheck_prof" -o run -- \
                  python tools/latency.py 8192 8193 32768 262144 ;;
-    b9) step bench_c1 600 python bench.py --steps 3 --cpu-sample 0 --extra none ;;
-    c2) step bench_c2 600 python bench.py --config c2 --steps 3 --cpu-sample 0 --extra none ;;
-    c3) step bench_c3 600 python bench.py --config c3 --steps 3 --cpu-sample 0 --extra none ;;
-    shard) step bench_shard 600 python bench.py --shard --steps 3 --cpu-sample 0 ;;
-    shardself) step bench_shard_self 600 python bench.py --shard --self-messages --steps 3 \
+    b9) step bench_c1 600 python bench.py --full --steps 3 --cpu-sample 0 --extra none ;;
+    c2) step bench_c2 600 python bench.py --full --config c2 --steps 3 --cpu-sample 0 --extra none ;;
+    c3) step bench_c3 600 python bench.py --full --config c3 --steps 3 --cpu-sample 0 --extra none ;;
+    shard) step bench_shard 600 python bench.py --full --shard --steps 3 --cpu-sample 0 ;;
+    shardself) step bench_shard_self 600 python bench.py --full --shard --self-messages --steps 3 \
                  --cpu-sample 0 ;;
-    shardspan8) step bench_shard_span8 600 python bench.py --shard --dist span8 --steps 3 \
+    shardspan8) step bench_shard_span8 600 python bench.py --full --shard --dist span8 --steps 3 \
                  --cpu-sample 0 ;;
     profiles) step profiles 1500 bash tools/round_profiles.sh "${PROFILE_TAG:-r06}" ;;
     lat) step latency 300 python tools/latency.py ;;
@@ -59,7 +59,7 @@ for s in "$@"; do
            step latency_midlevel 300 python tools/latency.py $LATN ;;
     phases) step phases_general 300 env SRS_MID_LEVEL_MAX=0 python tools/latency_phases.py $LATN &&
             step phases_midlevel 300 python tools/latency_phases.py $LATN ;;
-    bench) step bench_default 900 python bench.py ;;
+    bench) step bench_default 900 python bench.py --full ;;
     *) echo "unknown step $s"; exit 2 ;;
   esac
 done

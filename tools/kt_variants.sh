@@ -7,7 +7,7 @@ for v in $VARS; do
   rm -rf gpurun_out/kt/$v
   SRS_AMD_LIB=$PWD/simd-radix-sort_amd/lib/variants/$v/libsrs_amd.so timeout -k 10 300 \
     rocprofv3 --kernel-trace --output-format csv -d gpurun_out/kt/$v -o kt -- \
-    python bench.py --config ${CFG:-c1} --steps ${STEPS:-3} --warmup 1 --cpu-sample 0 --no-verify $EXTRA \
+    python bench.py --full --config ${CFG:-c1} --steps ${STEPS:-3} --warmup 1 --cpu-sample 0 --no-verify $EXTRA \
     > gpurun_out/kt/$v.log 2>&1; rc=$?
   echo "$v rc=$rc"; [ $rc -ne 0 ] && exit $rc
 done; exit 0

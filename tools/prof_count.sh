@@ -11,7 +11,7 @@ i=0
 for ctrs in "$P1" "$P2"; do
   i=$((i+1))
   timeout -k 10 300 rocprofv3 --pmc $ctrs --output-format csv -d $OUT/bench$i -o run \
-    -- python3 bench.py --config c2 --steps 2 --warmup 1 --extra none --cpu-sample 0 --no-verify \
+    -- python3 bench.py --full --config c2 --steps 2 --warmup 1 --extra none --cpu-sample 0 --no-verify \
     > $OUT/bench$i.log 2>&1 || { echo "bench pass $i rc=$?"; exit 1; }
   timeout -k 10 120 rocprofv3 --pmc $ctrs --output-format csv -d $OUT/probe$i -o run \
     -- ./tools/probe/count_probe > $OUT/probe$i.log 2>&1 || { echo "probe pass $i rc=$?"; exit 1; }

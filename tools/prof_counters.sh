@@ -9,9 +9,9 @@ ARGS="$@"
 mkdir -p $OUT
 run() {  # name, counters...
   local name=$1; shift
-  timeout -k 10 400 rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -o run -- python bench.py $ARGS --cpu-sample 0 --no-verify > $OUT/$name.log 2>&1
+  timeout -k 10 400 rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -o run -- python bench.py --full $ARGS --cpu-sample 0 --no-verify > $OUT/$name.log 2>&1
 }
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python bench.py $ARGS --cpu-sample 0 --no-verify > $OUT/trace.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python bench.py --full $ARGS --cpu-sample 0 --no-verify > $OUT/trace.log 2>&1
 run fetch FETCH_SIZE
 run write WRITE_SIZE
 run tcc TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum TCC_HIT_sum TCC_MISS_sum

@@ -11,7 +11,7 @@ st() { local n=$1 t=$2; shift 2; timeout -k 10 $t "$@" > $OUT/$n.txt 2>&1; local
 st latency 300 python tools/latency.py 16777216 33554432 67108864 125000000 134217728
 st phases 300 python tools/latency_phases.py 16777216 125000000 134217728
 st shard_trace 400 rocprofv3 --kernel-trace --stats -d $OUT/trace -o shard -- \
-  python bench.py --shard --steps 2 --warmup 1 --cpu-sample 0 --extra none --alloc-steps 0
+  python bench.py --full --shard --steps 2 --warmup 1 --cpu-sample 0 --extra none --alloc-steps 0
 tail -3 $OUT/latency.txt
 # outputs the library did not place: per-kernel times of the in-place arm
 st ab_outputs 400 python tools/ab_outputs.py --sets placed,inplace,plain,placed,inplace --rounds 5

@@ -8,7 +8,7 @@ mkdir -p $OUT
 run() {
   local name=$1; local ctrs=$2; shift 2
   timeout -k 10 300 rocprofv3 --pmc $ctrs --output-format csv -d $OUT/$name -o run \
-    -- python3 bench.py "$@" --cpu-sample 0 --no-verify > $OUT/$name.log 2>&1
+    -- python3 bench.py --full "$@" --cpu-sample 0 --no-verify > $OUT/$name.log 2>&1
   local rc=$?; echo "$name rc=$rc"; [ $rc -eq 0 ] || exit $rc
 }
 run sq1 "SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_INSTS_VALU SQ_INSTS_LDS" "$@"

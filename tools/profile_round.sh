@@ -12,11 +12,11 @@ TAG=$1; shift
 OUT=gpurun_out/prof/$TAG
 mkdir -p $OUT
 timeout -k 10 420 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run \
-  -- python3 bench.py "$@" > $OUT/bench_trace.log 2>&1 || { echo "trace rc=$?"; exit 1; }
+  -- python3 bench.py --full "$@" > $OUT/bench_trace.log 2>&1 || { echo "trace rc=$?"; exit 1; }
 echo "trace ok"
 timeout -k 10 420 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o run \
-  -- python3 bench.py "$@" --cpu-sample 0 > $OUT/bench_fetch.log 2>&1 || { echo "fetch rc=$?"; exit 1; }
+  -- python3 bench.py --full "$@" --cpu-sample 0 > $OUT/bench_fetch.log 2>&1 || { echo "fetch rc=$?"; exit 1; }
 echo "fetch ok"
 timeout -k 10 420 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -o run \
-  -- python3 bench.py "$@" --cpu-sample 0 > $OUT/bench_write.log 2>&1 || { echo "write rc=$?"; exit 1; }
+  -- python3 bench.py --full "$@" --cpu-sample 0 > $OUT/bench_write.log 2>&1 || { echo "write rc=$?"; exit 1; }
 echo "write ok"

@@ -86,7 +86,7 @@ def main(tag, src):
                       "hbm_bytes": 2 * fk + wk}
     stats = {short(r["Name"]): {"calls": int(r["Calls"]), "avg_ms": float(r["AverageNs"]) / 1e6}
              for r in rows}
-    doc = {"tag": tag, "command": " ".join(["python bench.py"] + sys.argv[3:]),
+    doc = {"tag": tag, "command": " ".join(["python bench.py --full"] + sys.argv[3:]),
            "workload": (line or {}).get("config", {}).get("workload"),
            "keys_per_gpu": (line or {}).get("config", {}).get("keys_per_gpu"),
            "correction": "read_bytes = 2 x FETCH_SIZE(KiB) x 1024 (gfx950, MI355X_MICROARCH.md HBM)",

@@ -12,11 +12,11 @@ st smoke 300 python __graft_entry__.py smoke
 st pytest_gpu 800 python -u -m pytest tests -m gpu -x -q --timeout 240 --timeout-method thread
 tail -2 $OUT/pytest_gpu.txt
 st shard_trace 400 rocprofv3 --kernel-trace --stats -d $OUT/trace -o shard -- \
-  python bench.py --shard --steps 2 --warmup 1 --cpu-sample 0 --extra none --alloc-steps 0
-B="python bench.py --shard --steps 5 --warmup 1 --cpu-sample 0 --extra none --alloc-steps 0"
+  python bench.py --full --shard --steps 2 --warmup 1 --cpu-sample 0 --extra none --alloc-steps 0
+B="python bench.py --full --shard --steps 5 --warmup 1 --cpu-sample 0 --extra none --alloc-steps 0"
 st shard_a1 300 $B
 st shard_b1 300 env SRS_SUPER_SCAN=0 $B
 st shard_a2 300 $B
 st shard_b2 300 env SRS_SUPER_SCAN=0 $B
-st bench 500 python bench.py
+st bench 500 python bench.py --full
 for f in shard_a1 shard_b1 shard_a2 shard_b2 bench; do python tools/show.py $OUT/$f.txt | cut -c1-160; done

@@ -9,5 +9,5 @@ st smoke 300 python __graft_entry__.py smoke
 st pytest_gpu 700 python -u -m pytest tests -m gpu -x -q --timeout 240 --timeout-method thread
 tail -2 gpurun_out/pytest_gpu.log
 bash tools/round_profiles.sh $1 || exit 1
-st bench 500 python bench.py
+st bench 500 python bench.py --full
 python tools/show.py gpurun_out/bench.log | cut -c1-400

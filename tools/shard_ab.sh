@@ -11,8 +11,8 @@ st() { local n=$1 t=$2; shift 2; timeout -k 10 $t "$@" > $OUT/$n.txt 2>&1; local
 st tests 600 python -u -m pytest tests/test_shard_gpu.py tests/test_gpu_sort.py -m gpu -x -q --timeout 240 --timeout-method thread
 tail -2 $OUT/tests.txt
 st shard_trace 400 rocprofv3 --kernel-trace --stats -d $OUT/trace -o shard -- \
-  python bench.py --shard --steps 2 --warmup 1 --cpu-sample 0 --extra none --alloc-steps 0
-B="python bench.py --shard --steps 5 --warmup 1 --cpu-sample 0 --extra none --alloc-steps 0"
+  python bench.py --full --shard --steps 2 --warmup 1 --cpu-sample 0 --extra none --alloc-steps 0
+B="python bench.py --full --shard --steps 5 --warmup 1 --cpu-sample 0 --extra none --alloc-steps 0"
 st shard_a1 300 $B
 st shard_b1 300 env SRS_PARTITION_PAIRS=0 $B
 st shard_a2 300 $B

@@ -11,7 +11,7 @@ for v in $VARS; do
   i=$((i+1))
   log=gpurun_out/sweep/${CFG:-c1}_${i}_$v.log
   SRS_AMD_LIB=$PWD/simd-radix-sort_amd/lib/variants/$v/libsrs_amd.so timeout -k 10 300 \
-    python bench.py --n $N --config ${CFG:-c1} --steps ${STEPS:-3} --cpu-sample 0 > $log 2>&1
+    python bench.py --full --n $N --config ${CFG:-c1} --steps ${STEPS:-3} --cpu-sample 0 > $log 2>&1
   rc=$?
   echo "$v rc=$rc $(python tools/show.py $log | cut -d' ' -f2-)" | cut -c1-300
   if [ $rc -ge 124 ] || [ $rc -eq 134 ] || [ $rc -eq 139 ]; then exit $rc; fi
