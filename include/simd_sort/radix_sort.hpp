@@ -35,6 +35,7 @@
 #include <string>
 #include <tuple>
 #include <type_traits>
+#include <utility>
 
 #include "../srs_c_api.h"
 
@@ -258,6 +259,38 @@ void sort(void* stream, const SortIndex num, DataElement<K, Ps...>* const elemen
                                     (void*)elements, (uint32_t)sizeof(DataElement<K, Ps...>),
                                     nullptr, stream),
                 "device::sort");
+}
+
+// top_k: the first min(k, num) records of the stable sort of the input
+// (srs_topk_soa_device: Up the k smallest ascending, !Up the k largest
+// descending, equal keys in input order), written to keys_out and to the
+// second array of every payload pair {payload, payload_out}. The inputs are
+// not written; the outputs must not overlap them.
+template <bool Up = true, typename K, typename... Ps>
+void top_k(void* stream, const SortIndex k, const SortIndex num, const K* const keys,
+           K* const keys_out, std::pair<const Ps*, Ps*>... payloads) {
+  static_assert(detail::key_kind<K>() >= 0, "unsupported key type");
+  static_assert((detail::valid_payload<Ps> && ...), "payload sizes must be 1, 2, 4 or 8");
+  static_assert(sizeof...(Ps) <= SRS_MAX_PAYLOADS, "too many payload arrays");
+  const void* pays[sizeof...(Ps) + 1] = {(const void*)payloads.first..., nullptr};
+  void* pays_out[sizeof...(Ps) + 1] = {(void*)payloads.second..., nullptr};
+  uint32_t sizes[sizeof...(Ps) + 1] = {(uint32_t)sizeof(Ps)..., 0};
+  detail::check(srs_topk_soa_device((int64_t)num, (int64_t)k, detail::key_kind<K>(), Up ? 1 : 0,
+                                    (const void*)keys, (int32_t)sizeof...(Ps), pays, sizes,
+                                    (void*)keys_out, pays_out, nullptr, stream),
+                "device::top_k");
+}
+
+template <bool Up = true, typename K, typename... Ps>
+void top_k(void* stream, const SortIndex k, const SortIndex num,
+           const DataElement<K, Ps...>* const elements, DataElement<K, Ps...>* const elements_out) {
+  static_assert(is_power_of_two<sizeof(DataElement<K, Ps...>)>,
+                "size of DataElement<K, Ps...> must be a power of two");
+  static_assert(detail::key_kind<K>() >= 0, "unsupported key type");
+  detail::check(srs_topk_aos_device((int64_t)num, (int64_t)k, detail::key_kind<K>(), Up ? 1 : 0,
+                                    (const void*)elements, (uint32_t)sizeof(DataElement<K, Ps...>),
+                                    (void*)elements_out, nullptr, stream),
+                "device::top_k");
 }
 
 }  // namespace device

@@ -166,6 +166,38 @@ int srs_sort_segments_device(int64_t num, int key_kind, int up, void* keys,
                              const int64_t* segment_bounds, int32_t known_top_bits,
                              void* stream);
 
+/* Top-k: writes the first min(k, num) records of the stable sort of the
+ * input (by the key order above; up == 0 reversed, so up = 1 gives the k
+ * smallest ascending and up = 0 the k largest descending) to the *_out
+ * arrays, without sorting the rest. Equal keys keep their input order, so the
+ * result is unique: bit-equal to the head of srs_sort_soa_device with
+ * num > cmp_sort_threshold. Float keys follow the total order (-0.0 before
+ * +0.0 ascending) at every size; NaN keys are outside the contract. The
+ * inputs are never written; the outputs hold min(k, num) records and must
+ * not overlap any input (SRS_ERR_INVALID_ARG, checked before any device
+ * access). k <= 0 or num <= 0 is a no-op; k >= num is the out-of-place sort.
+ * indices_out (device int64, may be NULL) receives each output record's
+ * position in the input (ascending within a run of equal keys); it travels
+ * as one more 8-byte column, so with it at most SRS_MAX_PAYLOADS - 1 = 63
+ * payload columns are allowed (SRS_ERR_UNSUPPORTED). The reference has no
+ * counterpart (its callers sort everything and keep the head).
+ * The call enqueues work on `stream` and blocks on a small pinned read-back
+ * once per select pass (a 12-bit digit histogram of the keys that share the
+ * prefix found so far; one to three passes for most inputs, and none when
+ * k > num / 2 or num <= 8192: those calls sort everything into a workspace
+ * buffer and copy the head); the finishing sort of the selected records
+ * reads back as srs_sort_soa_device does for its size. Results are ready
+ * when the stream completes. */
+int srs_topk_soa_device(int64_t num, int64_t k, int key_kind, int up,
+                        const void* keys, int32_t num_payloads,
+                        const void* const* payloads, const uint32_t* payload_sizes,
+                        void* keys_out, void* const* payloads_out,
+                        int64_t* indices_out, void* stream);
+/* The same on combined elements (srs_sort_aos_device's layout). */
+int srs_topk_aos_device(int64_t num, int64_t k, int key_kind, int up,
+                        const void* elements, uint32_t elem_size,
+                        void* elements_out, int64_t* indices_out, void* stream);
+
 /* ---- multi-GPU shard primitives (top-radix-bits partition) --
  * A node-wide sort of one array spread over N GPUs: every rank histograms
  * its keys' top bits (srs_key_histogram_device), the histograms are summed
@@ -423,6 +455,18 @@ int srs_debug_plan_table(const uint32_t* hist, int64_t num, int key_bits, int32_
 
 /* Release cached device workspaces (for leak checks / shutdown). */
 int srs_release_workspace(void);
+
+/* Test hook, process-wide, like srs_debug_set_super_scan: the top-k select
+ * stops refining once the boundary bucket holds <= max_candidates records
+ * (<= 0 restores the default, 2^20), so that multi-pass refinement runs at
+ * small n. */
+int srs_debug_set_topk_candidates(int64_t max_candidates);
+
+/* Select passes over the input and records handed to the finishing sort in
+ * the last top-k on the current device (synchronizes the device). Tests use
+ * it to prove which path an input took. info[0] = passes, info[1] = records
+ * sorted, info[2] = 1 if the call took the full-sort route. */
+int srs_debug_last_topk(int64_t* info);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstring>
 #include <cstdio>
@@ -550,6 +551,12 @@ struct Workspace {
   int64_t gorder_cap = 0;
   DevBuf mid;  // mid-size single launch: the tiles' key OR / AND, their digit counts
   DevBuf midbar;  // and its grid barrier's words (zeroed once)
+  // top-k: the compact columns of the selected records, the select pass's
+  // histogram row, the tally's tile counts / bases / scan temp, the gather's
+  // column descriptor; the row's pinned copy; what the last call did
+  DevBuf sel, selhist, selcnt, seldesc;
+  unsigned long long* h_sel = nullptr;
+  int64_t topk_info[3] = {0, 0, 0};
   hipStream_t side = nullptr;  // medium sorts: the large local class's stream
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   ListCounters* h_ctr = nullptr;
@@ -584,9 +591,10 @@ struct Workspace {
                       &fallback2, &redo, &redo2, &shist, &lut, &lut_rbits, &copy, &plan, &tcount,
                       &gcount, &tbase, &gbase, &var, &sbase, &tile_seg, &group_seg, &hist, &offs,
                       &gsum, &gofs, &scan_tmp, &totals, &ctr, &prun, &ptile, &btot, &bnt, &btile,
-                      &nt_over, &gtile, &gorder, &mid, &midbar};
+                      &nt_over, &gtile, &gorder, &mid, &midbar, &sel, &selhist, &selcnt, &seldesc};
     for (DevBuf* b : bufs) free_buf(*b);
     for (auto& t : small_taken) free_buf(t.second);
+    if (h_sel) (void)hipHostFree(h_sel);
     if (h_ctr) (void)hipHostFree(h_ctr);
     if (h_totals) (void)hipHostFree(h_totals);
     if (h_mid) (void)hipHostFree(h_mid);
@@ -2319,6 +2327,291 @@ int sort_device(Request& R, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------
+// top-k: select the records that can be among the first k by
+// walking down the key's digits, compact them in input order, sort that set
+// ---------------------------------------------------------------------------
+// The select stops refining once the boundary bucket holds this many
+// records: the finishing sort of k + 2^20 records of a small k is then the
+// single-launch sort (kMidMaxKeys), ~0.1 ms, where one more pass would read
+// the whole key column again (srs_debug_set_topk_candidates).
+constexpr int64_t kTopkCandidates = kMidMaxKeys;
+std::atomic<int64_t> g_topk_candidates{kTopkCandidates};
+// Above k = num / 2 the select saves less than it costs: those calls sort
+// everything. Measured at 1e9 u64 + u64 records the two routes cross at
+// k = 0.52-0.54 num (the byte model, 24 n + 176 k against the
+// sort's 112 n + 32 k, said 0.61); at num / 2 the select still wins by 3-6 %.
+// Inputs of one local sort (num <= kLocalCap) are sorted whole as well.
+constexpr int64_t kTopkFullPercent = 50;
+// (SRS_TOPK_FULL_PCT overrides the percentage, for crossover measurements:
+// tools/topk_bench.py; read on every call)
+int64_t topk_full_percent() {
+  const char* e = getenv("SRS_TOPK_FULL_PCT");
+  return (e && *e) ? atoll(e) : kTopkFullPercent;
+}
+
+// The columns a top-k call moves, with their views in the input and in the
+// caller's output: SoA columns as they are; an AoS record as its key and the
+// rest of its bytes in aligned power-of-two pieces of up to 8 bytes, so that
+// the compact set is always SoA columns with the key column first.
+struct TopkLayout {
+  int nc = 0;
+  uint32_t width[SRS_MAX_COLS];
+  char* in[SRS_MAX_COLS];
+  char* out[SRS_MAX_COLS];
+  uint32_t stride[SRS_MAX_COLS];  // of both views
+};
+
+void topk_layout(const Request& R, TopkLayout& L) {
+  if (!R.aos) {
+    L.nc = R.ncols;
+    for (int c = 0; c < R.ncols; c++) {
+      L.width[c] = L.stride[c] = R.widths[c];
+      L.in[c] = (char*)R.in_cols[c];
+      L.out[c] = (char*)R.out_cols[c];
+    }
+    return;
+  }
+  const uint32_t E = R.elem_size;
+  uint32_t off = 0, w = (uint32_t)key_size_of(R.kind);
+  while (off < E) {
+    L.width[L.nc] = w;
+    L.stride[L.nc] = E;
+    L.in[L.nc] = (char*)R.in_cols[0] + off;
+    L.out[L.nc] = (char*)R.out_cols[0] + off;
+    L.nc++;
+    off += w;
+    w = std::min<uint32_t>(8, off & (~off + 1));  // (E is a power of two: never past the record)
+  }
+}
+
+// A sort under the caller's workspace lock and WsUse, on the same stream
+// (as the shard's segment sorts): sort_device without the locking.
+int sort_locked(Workspace* W, const Request& R, hipStream_t st) {
+  if (R.num <= 1) return copy_through(R, st);
+  if (R.num <= kLocalCap) return run_small(W, R, st);
+  return run_sort(W, R, st);
+}
+
+int topk_device(const Request& R, int64_t k, int64_t* idx_out, hipStream_t st) {
+  const int64_t n = R.num;
+  k = std::min(k, n);
+  const int ks = key_size_of(R.kind);
+  Workspace* W = nullptr;
+  WsLock lk;
+  SRS_TRY(acquire_ws(&W, &lk));
+  WsUse use;
+  SRS_TRY(use.begin(W, st));
+  const bool full = n <= kLocalCap || (__int128)k * 100 > (__int128)n * topk_full_percent();
+  if (k >= n && !idx_out) {  // the plain out-of-place sort
+    W->topk_info[0] = 0;
+    W->topk_info[1] = n;
+    W->topk_info[2] = 1;
+    return sort_locked(W, R, st);
+  }
+  TopkLayout L;
+  topk_layout(R, L);
+  SortDesc kd;
+  memset(&kd, 0, sizeof kd);
+  key_masks(R.kind, R.up, kd);
+  SelectArgs a;
+  memset(&a, 0, sizeof a);
+  a.keys = L.in[0];
+  a.stride = L.stride[0];
+  a.n = n;
+  a.all = 1;
+  a.key_bits = kd.key_bits;
+  a.mpos = kd.mpos;
+  a.mneg = kd.mneg;
+
+  // ---- which records: the prefix of the boundary bucket ---------------------
+  int64_t passes = 0, limit = n;  // limit: records the compact set holds
+  if (!full) {
+    SRS_TRY(ensure(W->selhist, kSelHistWords * sizeof(uint64_t)));
+    if (!W->h_sel)
+      HIP_TRY(hipHostMalloc((void**)&W->h_sel, kSelHistWords * sizeof(uint64_t), hipHostMallocDefault));
+    const int kb = kd.key_bits;
+    const uint64_t kmask = kb == 64 ? ~0ull : ((1ull << kb) - 1);
+    const int64_t maxc = g_topk_candidates.load();
+    uint64_t prefix = 0;  // the fixed top bits, in place
+    int fixed = 0, top = kb;  // the next digit ends below bit `top`
+    int64_t k_rem = k, cand = n;  // the rank wanted inside the prefix's bucket; its size
+    bool resolved = false;        // the bucket's keys are all equal
+    for (;;) {
+      a.bits = std::min(kHistMaxBits, top);
+      a.shift = top - a.bits;
+      a.all = fixed == 0;
+      a.psh = fixed ? kb - fixed : 0;
+      a.pv = fixed ? prefix >> a.psh : 0;
+      HIP_TRY(hipMemsetAsync(W->selhist.p, 0, kSelHistWords * sizeof(uint64_t), st));
+      {
+        TimedScope ts("select_hist", (double)n, st);
+        launch_select_hist(ks, a, (unsigned long long*)W->selhist.p, st);
+      }
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(W->h_sel, W->selhist.p, kSelHistWords * sizeof(uint64_t),
+                             hipMemcpyDeviceToHost, st));
+      SRS_TRY(sync_poll(st));
+      passes++;
+      const unsigned long long* h = W->h_sel;
+      int64_t below = 0;
+      int b = 0;
+      const int nb = 1 << a.bits;
+      for (; b < nb; b++) {
+        if (below + (int64_t)h[b] >= k_rem) break;
+        below += (int64_t)h[b];
+      }
+      if (b == nb) return fail(SRS_ERR_INTERNAL, "top-k: the histogram holds fewer keys than its bucket");
+      k_rem -= below;
+      cand = (int64_t)h[b];
+      prefix |= (uint64_t)b << a.shift;
+      fixed = kb - a.shift;
+      // where the bucket's parent still varies below this digit: the next
+      // digit starts at its highest varying bit, the bits between are shared
+      const uint64_t low = (1ull << a.shift) - 1;  // (shift <= 52)
+      const uint64_t vand = ~h[kSelOrSlot + 1] & kmask;
+      const uint64_t var = (h[kSelOrSlot] ^ vand) & low;
+      if (var == 0) {
+        resolved = true;
+        prefix |= vand & low;
+        fixed = kb;
+      }
+      if (resolved || cand == k_rem || cand <= maxc) break;
+      const int hb = 63 - __builtin_clzll(var);
+      prefix |= vand & low & ~((2ull << hb) - 1);
+      fixed = kb - (hb + 1);
+      top = hb + 1;
+    }
+    a.all = 0;
+    a.psh = kb - fixed;
+    a.pv = prefix >> a.psh;
+    // everything below the prefix, and the bucket itself (a bucket of equal
+    // keys: only its first k_rem records, in input order)
+    limit = (k - k_rem) + (resolved ? k_rem : cand);
+  }
+  const int64_t m = limit;
+
+  // ---- the compact columns ---------------------------------------------------
+  const int nsc = L.nc + (idx_out ? 1 : 0);
+  size_t off[SRS_MAX_COLS + 1], bytes = 0;
+  for (int c = 0; c < nsc; c++) {
+    off[c] = bytes;
+    bytes += align_up((size_t)m * (c < L.nc ? L.width[c] : 8), 256);
+  }
+  SRS_TRY(ensure(W->sel, bytes, ws_alloc_mode()));
+  SRS_TRY(ensure(W->seldesc, sizeof(SortDesc)));
+  char* sel = (char*)W->sel.p;
+  int64_t* sel_idx = idx_out ? (int64_t*)(sel + off[L.nc]) : nullptr;
+  Request S;  // the compact set's sort, in place
+  S.num = m;
+  S.kind = R.kind;
+  S.up = R.up;
+  S.thresh = 0;  // (the total order for floats at every size)
+  S.aos = false;
+  S.elem_size = 0;
+  S.ncols = nsc;
+  for (int c = 0; c < nsc; c++) {
+    S.in_cols[c] = S.out_cols[c] = sel + off[c];
+    S.widths[c] = c < L.nc ? L.width[c] : 8;
+  }
+  W->topk_info[0] = passes;
+  W->topk_info[1] = m;
+  W->topk_info[2] = full ? 1 : 0;
+
+  if (full && !R.aos && !idx_out) {
+    // SoA columns: sorted straight into the compact columns
+    Request F = R;
+    F.thresh = 0;
+    for (int c = 0; c < nsc; c++) F.out_cols[c] = S.out_cols[c];
+    SRS_TRY(sort_locked(W, F, st));
+  } else {
+    SortDesc d;
+    memset(&d, 0, sizeof d);
+    key_masks(R.kind, R.up, d);
+    for (int c = 0; c < L.nc; c++)
+      d.cols[c] = Col{{L.in[c], sel + off[c], nullptr, nullptr}, L.width[c],
+                      {L.stride[c], L.width[c], L.width[c], L.width[c]}};
+    d.key = d.cols[0];
+    d.ncols = L.nc;
+    launch_set_desc(d, (SortDesc*)W->seldesc.p, st);
+    const uint64_t* tbase = nullptr;
+    if (!full) {
+      const int64_t ntiles = (n + kTile - 1) / kTile;
+      const int64_t rows = 2 * ntiles;
+      SRS_TRY(ensure(W->selcnt, (size_t)(2 * rows + scan_temp_elems(rows) + 1) * sizeof(uint64_t)));
+      uint64_t* counts = (uint64_t*)W->selcnt.p;
+      uint64_t* bases = counts + rows;
+      uint64_t* temp = bases + rows;
+      {
+        TimedScope ts("select_tally", (double)n, st);
+        launch_select_tally(ks, a, counts, st);
+      }
+      launch_excl_scan(counts, bases, rows, temp, temp + scan_temp_elems(rows), st);
+      tbase = bases;
+    }
+    {
+      TimedScope ts("select_gather", (double)m, st);
+      launch_select_gather(ks, a, (const SortDesc*)W->seldesc.p, tbase, limit, sel_idx, st);
+    }
+    HIP_TRY(hipGetLastError());
+    SRS_TRY(sort_locked(W, S, st));
+  }
+
+  // ---- the first k records to the caller's arrays ----------------------------
+  SortDesc d;
+  memset(&d, 0, sizeof d);
+  key_masks(R.kind, R.up, d);
+  for (int c = 0; c < nsc; c++) {
+    const uint32_t w = S.widths[c];
+    char* out = c < L.nc ? L.out[c] : (char*)idx_out;
+    d.cols[c] = Col{{sel + off[c], out, nullptr, nullptr}, w, {w, c < L.nc ? L.stride[c] : 8u, w, w}};
+  }
+  d.key = d.cols[0];
+  d.ncols = nsc;
+  launch_set_desc(d, (SortDesc*)W->seldesc.p, st);
+  SelectArgs f = a;
+  f.keys = sel;
+  f.stride = (uint32_t)ks;
+  f.n = k;
+  f.all = 1;
+  {
+    TimedScope ts("select_gather", (double)k, st);
+    launch_select_gather(ks, f, (const SortDesc*)W->seldesc.p, nullptr, k, nullptr, st);
+  }
+  HIP_TRY(hipGetLastError());
+  return SRS_OK;
+}
+
+bool ranges_overlap(const void* a, size_t an, const void* b, size_t bn) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return an && bn && x < y + bn && y < x + an;
+}
+
+// What the top-k entry points check after the request is built, all before
+// the first device access: NULL arrays, alignment, outputs clear of inputs.
+int topk_validate(const Request& R, int64_t k, const void* out0, const int64_t* idx_out) {
+  const int64_t kk = std::min(k, R.num);
+  if (!R.in_cols[0]) return fail(SRS_ERR_INVALID_ARG, R.aos ? "elements is NULL" : "keys is NULL");
+  if (!out0) return fail(SRS_ERR_INVALID_ARG, R.aos ? "elements_out is NULL" : "keys_out is NULL");
+  for (int c = 0; c < R.ncols; c++) {
+    if (!R.in_cols[c] || !R.out_cols[c]) return fail(SRS_ERR_INVALID_ARG, "payload pointer is NULL");
+    const uint32_t al = R.aos ? (R.elem_size < 8 ? R.elem_size : 8) : R.widths[c];
+    if (((uintptr_t)R.in_cols[c] | (uintptr_t)R.out_cols[c]) % al != 0)
+      return fail(SRS_ERR_INVALID_ARG, "device arrays must be aligned to their element size "
+                                       "(records: to min(elem_size, 8))");
+  }
+  if ((uintptr_t)idx_out % 8 != 0) return fail(SRS_ERR_INVALID_ARG, "indices_out must be 8-byte aligned");
+  for (int o = 0; o <= R.ncols; o++) {
+    const void* op = o < R.ncols ? R.out_cols[o] : (const void*)idx_out;
+    const size_t ob = (size_t)kk * (o < R.ncols ? R.widths[o] : 8);
+    if (!op) continue;
+    for (int c = 0; c < R.ncols; c++)
+      if (ranges_overlap(op, ob, R.in_cols[c], (size_t)R.num * R.widths[c]))
+        return fail(SRS_ERR_INVALID_ARG, "top-k outputs must not overlap the inputs");
+  }
+  return SRS_OK;
+}
+
+// ---------------------------------------------------------------------------
 // host arrays (the reference's calling convention, radixSort.hpp:1780):
 // staged PCIe copies, and the split of one host array over several GPUs
 // ---------------------------------------------------------------------------
@@ -3065,6 +3358,32 @@ int srs_sort_aos_device(int64_t num, int key_kind, int up, int64_t cmp_sort_thre
   return sort_device(R, (hipStream_t)stream);
 }
 
+int srs_topk_soa_device(int64_t num, int64_t k, int key_kind, int up, const void* keys,
+                        int32_t num_payloads, const void* const* payloads,
+                        const uint32_t* payload_sizes, void* keys_out, void* const* payloads_out,
+                        int64_t* indices_out, void* stream) {
+  Request R;
+  SRS_TRY(build_soa(R, num, key_kind, up, 0, (void*)keys, num_payloads, (void* const*)payloads,
+                    payload_sizes, keys_out, payloads_out));
+  if (indices_out && num_payloads > SRS_MAX_PAYLOADS - 1)
+    return fail(SRS_ERR_UNSUPPORTED,
+                "indices_out travels as one more payload column: at most 63 payload columns "
+                "with it");
+  if (k <= 0 || num <= 0) return SRS_OK;
+  SRS_TRY(topk_validate(R, k, keys_out, indices_out));
+  return topk_device(R, k, indices_out, (hipStream_t)stream);
+}
+
+int srs_topk_aos_device(int64_t num, int64_t k, int key_kind, int up, const void* elements,
+                        uint32_t elem_size, void* elements_out, int64_t* indices_out,
+                        void* stream) {
+  Request R;
+  SRS_TRY(build_aos(R, num, key_kind, up, 0, (void*)elements, elem_size, elements_out));
+  if (k <= 0 || num <= 0) return SRS_OK;
+  SRS_TRY(topk_validate(R, k, elements_out, indices_out));
+  return topk_device(R, k, indices_out, (hipStream_t)stream);
+}
+
 int srs_fill_synthetic_device(int64_t num, int key_kind, uint64_t seed, uint64_t first_index,
                               void* keys, int32_t num_payloads, void* const* payloads,
                               const uint32_t* payload_sizes, void* stream) {
@@ -3375,6 +3694,21 @@ int srs_release_workspace(void) {
   }
   old.clear();  // each workspace is freed by its last holder (~Workspace)
   (void)hipGetLastError();
+  return SRS_OK;
+}
+
+int srs_debug_set_topk_candidates(int64_t max_candidates) {
+  g_topk_candidates.store(max_candidates > 0 ? max_candidates : kTopkCandidates);
+  return SRS_OK;
+}
+
+int srs_debug_last_topk(int64_t* info) {
+  if (!info) return fail(SRS_ERR_INVALID_ARG, "info is NULL");
+  Workspace* W = nullptr;
+  WsLock lk;
+  SRS_TRY(acquire_ws(&W, &lk));
+  HIP_TRY(hipDeviceSynchronize());
+  for (int i = 0; i < 3; i++) info[i] = W->topk_info[i];
   return SRS_OK;
 }
 

@@ -130,4 +130,37 @@ void set_xcd_rotation(int mode);
 void launch_copy_list(const SortDesc* d, const Seg* segs, int64_t nsegs, uint64_t* chunks,
                       uint64_t* cbase, uint64_t* scan_temp, uint64_t* total, hipStream_t st);
 
+
+// ---- top-k select ------------------------------------------
+// What the select kernels know of the key column and of the prefix found so
+// far: record i's key is at keys + i * stride; a key matches when its
+// transformed bits u satisfy u >> psh == pv (all != 0: no prefix yet, every
+// key matches).
+struct SelectArgs {
+  const char* keys;
+  uint32_t stride;
+  int32_t all;
+  int64_t n;
+  uint64_t pv;
+  int32_t psh;
+  int32_t shift, bits;  // select_hist: digit = (u >> shift) & (2^bits - 1), bits <= kHistMaxBits
+  int32_t key_bits;
+  uint64_t mpos, mneg;  // SortDesc's key transform
+};
+// select_hist's output row: 2^kHistMaxBits u64 bins, then the OR of the
+// matching keys and the OR of their complements (zeroed by the caller)
+constexpr int kSelOrSlot = 1 << kHistMaxBits;
+constexpr int kSelHistWords = kSelOrSlot + 2;
+void launch_select_hist(int key_size, const SelectArgs& a, unsigned long long* hist,
+                        hipStream_t st);
+// counts: 2 * ntiles u64 (ntiles = ceil(n / kTile)): per tile the keys below
+// the prefix, then per tile the keys equal to it
+void launch_select_tally(int key_size, const SelectArgs& a, uint64_t* counts, hipStream_t st);
+// tbase: the exclusive scan of the tally's row; tbase == nullptr (with
+// a.all): an ordered copy of the first `limit` records. Columns: d's BUF_IN
+// -> BUF_OUT views, cols[0] the key column; no destination record >= limit
+// is written.
+void launch_select_gather(int key_size, const SelectArgs& a, const SortDesc* d,
+                          const uint64_t* tbase, int64_t limit, int64_t* idx_out, hipStream_t st);
+
 }  // namespace srs

@@ -4904,4 +4904,296 @@ void launch_start(const SortDesc& d, SortDesc* out, Seg seg0, int to_local, Seg*
 }
 
 
+
+// ---------------------------------------------------------------------------
+// top-k select (srs_topk_soa_device / srs_topk_aos_device)
+//
+// The host walks down the key from its top bits: select_hist_kernel counts a
+// digit of the keys that share the prefix found so far, the host picks the
+// bucket that holds rank k and descends. Once the boundary bucket is small
+// enough, select_tally_kernel counts per tile the keys below the prefix
+// ("sure") and equal to it ("candidates"), launch_excl_scan turns the counts
+// into tile bases and select_gather_kernel writes the selected records, in
+// input order, to a compact buffer that the sort then finishes. Three
+// launches in stream order: no workgroup ever waits for another.
+// ---------------------------------------------------------------------------
+constexpr int kSelThreads = 256;
+constexpr int kSelItems = kTile / kSelThreads;
+static_assert(kSelItems * kSelThreads == kTile, "select block shape");
+static_assert(kSelThreads == 256 && kSelItems == 16, "the gather scans 16 x 4 wave counts in one wave");
+
+template <typename U>
+__device__ __forceinline__ Xform<U> select_xform(const SelectArgs& a) {
+  Xform<U> xf;
+  xf.mpos = (U)a.mpos;
+  xf.cdiff = (U)(a.mpos ^ a.mneg);
+  xf.negzero = 0;
+  xf.sbit = a.key_bits - 1;
+  xf.canon = false;
+  return xf;
+}
+
+// The tile's keys, kSelItems per thread. A full tile of a dense, 16-byte
+// aligned key column is read 16 bytes per lane (slot order then differs from
+// element order: for the order-free counts only); otherwise slot k of thread
+// t is element k * kSelThreads + t, zero past the tile's end.
+template <typename KT, typename U, bool VEC_OK>
+__device__ __forceinline__ void select_load(const SelectArgs& a, int64_t base, int cnt,
+                                            U (&raw)[kSelItems]) {
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  constexpr int KS = (int)sizeof(KT);
+  constexpr int VPL = 16 / KS;  // keys per 16-byte load
+  if (VEC_OK && cnt == kTile && a.stride == (uint32_t)KS && ((uintptr_t)a.keys & 15) == 0) {
+    const char* p = a.keys + base * KS + (int64_t)threadIdx.x * 16;
+#pragma unroll
+    for (int j = 0; j < kSelItems / VPL; j++) {
+      const u32x4 v = gld<u32x4>(p + (int64_t)j * kSelThreads * 16);
+#pragma unroll
+      for (int i = 0; i < VPL; i++) {
+        if constexpr (KS == 8) raw[j * VPL + i] = (U)((uint64_t)v[2 * i] | ((uint64_t)v[2 * i + 1] << 32));
+        else if constexpr (KS == 4) raw[j * VPL + i] = (U)v[i];
+        else raw[j * VPL + i] = (U)((v[i * KS / 4] >> (8 * ((i * KS) % 4))) & ((1u << (8 * KS)) - 1u));
+      }
+    }
+  } else {
+    const char* p = a.keys + base * (int64_t)a.stride;
+#pragma unroll
+    for (int k = 0; k < kSelItems; k++) {
+      const int e = k * kSelThreads + (int)threadIdx.x;
+      raw[k] = e < cnt ? (U)gld<KT>(p + (int64_t)e * a.stride) : (U)0;
+    }
+  }
+}
+
+// Adds the histogram of digit [shift, shift + bits) of the keys that match
+// the prefix to hist[0 .. 2^bits), the OR of those keys to hist[kSelOrSlot]
+// and the OR of their complements (the AND, inverted: zero-initialised like
+// the bins) to hist[kSelOrSlot + 1].
+template <typename KT, typename U>
+__global__ __launch_bounds__(kSelThreads) void select_hist_kernel(
+    const SelectArgs a, int64_t ntiles, unsigned long long* __restrict__ hist) {
+  constexpr uint32_t kSpare = 1u << kHistMaxBits;  // keys outside the prefix / past the end
+  __shared__ uint32_t h[1 << kHistMaxBits];
+  __shared__ unsigned long long sor[2];
+  const uint32_t nb = 1u << a.bits;
+  for (uint32_t i = threadIdx.x; i < nb; i += kSelThreads) h[i] = 0;
+  if (threadIdx.x < 2) sor[threadIdx.x] = 0;
+  __syncthreads();
+  const Xform<U> xf = select_xform<U>(a);
+  const U pv = (U)a.pv;
+  const uint32_t mask = nb - 1;
+  U vor = 0, vnand = 0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t base = tile * kTile;
+    const int cnt = (int)min((int64_t)kTile, a.n - base);
+    U raw[kSelItems];
+    select_load<KT, U, true>(a, base, cnt, raw);
+    const bool full = cnt == kTile;
+#pragma unroll
+    for (int k = 0; k < kSelItems; k++) {
+      const U u = xf(raw[k]);
+      // (a partial tile is always read in element order)
+      bool ok = full || k * kSelThreads + (int)threadIdx.x < cnt;
+      ok = ok && (a.all || (U)(u >> a.psh) == pv);
+      vor |= ok ? u : (U)0;
+      vnand |= ok ? (U)~u : (U)0;
+      const uint32_t d = ok ? ((uint32_t)(u >> a.shift) & mask) : kSpare;
+      // A wave's 64 consecutive keys often share their digit (sorted or
+      // constant input; below the first pass nearly every key is outside the
+      // prefix): the lanes that agree with the leading lane add once.
+      const uint32_t d0 = __builtin_amdgcn_readfirstlane(d);
+      const uint64_t same = __ballot(d == d0);
+      if (d != d0) {
+        if (d != kSpare) atomicAdd(&h[d], 1u);
+      } else if (lane_id() == 0 && d0 != kSpare) {
+        atomicAdd(&h[d0], (uint32_t)__popcll(same));
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    vor |= __shfl_xor(vor, o, 64);
+    vnand |= __shfl_xor(vnand, o, 64);
+  }
+  if (lane_id() == 0) {
+    atomicOr(&sor[0], (unsigned long long)vor);
+    atomicOr(&sor[1], (unsigned long long)vnand);
+  }
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < nb; i += kSelThreads)
+    if (h[i]) atomicAdd(&hist[i], (unsigned long long)h[i]);
+  if (threadIdx.x < 2 && sor[threadIdx.x]) atomicOr(&hist[kSelOrSlot + threadIdx.x], sor[threadIdx.x]);
+}
+
+// counts[tile] = the tile's keys below the prefix, counts[ntiles + tile] = its
+// keys equal to it (one row of 2 * ntiles: its exclusive scan puts the
+// candidates behind all sure records).
+template <typename KT, typename U>
+__global__ __launch_bounds__(kSelThreads) void select_tally_kernel(
+    const SelectArgs a, int64_t ntiles, uint64_t* __restrict__ counts) {
+  __shared__ uint32_t wc[2][kSelThreads / 64];
+  const int64_t tile = blockIdx.x;
+  const int64_t base = tile * kTile;
+  const int cnt = (int)min((int64_t)kTile, a.n - base);
+  const Xform<U> xf = select_xform<U>(a);
+  const U pv = (U)a.pv;
+  U raw[kSelItems];
+  select_load<KT, U, true>(a, base, cnt, raw);
+  const bool full = cnt == kTile;
+  uint32_t ns = 0, nc = 0;  // wave-uniform
+#pragma unroll
+  for (int k = 0; k < kSelItems; k++) {
+    const bool ok = full || k * kSelThreads + (int)threadIdx.x < cnt;
+    const U x = (U)(xf(raw[k]) >> a.psh);
+    ns += (uint32_t)__popcll(__ballot(ok && !a.all && x < pv));
+    nc += (uint32_t)__popcll(__ballot(ok && (a.all || x == pv)));
+  }
+  if (lane_id() == 0) {
+    wc[0][threadIdx.x >> 6] = ns;
+    wc[1][threadIdx.x >> 6] = nc;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    uint32_t s = 0;
+    for (int w = 0; w < kSelThreads / 64; w++) s += wc[threadIdx.x][w];
+    counts[threadIdx.x * ntiles + tile] = s;
+  }
+}
+
+// The stable compaction: the tile's sure records go to tbase[tile] + rank,
+// its candidates to tbase[ntiles + tile] + rank (ranks in input order), for
+// as long as the position stays below `limit` (the k - sure first candidates
+// when the key is resolved). Every column of *desc moves from its BUF_IN
+// view to its BUF_OUT view (cols[0] is the key column); idx_out, when set,
+// receives the record's input position. a.all without tbase: position =
+// input position (an ordered copy of the first `limit` records).
+template <typename KT, typename U>
+__global__ __launch_bounds__(kSelThreads) void select_gather_kernel(
+    const SelectArgs a, const SortDesc* __restrict__ desc, const uint64_t* __restrict__ tbase,
+    int64_t ntiles, int64_t limit, int64_t* __restrict__ idx_out) {
+  __shared__ uint32_t wcnt[2][kSelItems * (kSelThreads / 64)];  // [sure / cand][slot][wave]
+  const int64_t tile = blockIdx.x;
+  const int64_t base = tile * kTile;
+  const int cnt = (int)min((int64_t)kTile, a.n - base);
+  const int t = (int)threadIdx.x, wave = t >> 6;
+  if (tbase != nullptr) {
+    // A tile the tally found nothing in, or whose candidates all lie past
+    // the limit (a bucket of equal keys: every tile behind the first k_rem
+    // candidates), has nothing to write: it does not read its keys again.
+    const uint64_t s0 = tbase[tile], s1 = tbase[tile + 1];  // ([ntiles]: the first candidate base)
+    const uint64_t c0 = tbase[ntiles + tile];
+    const bool no_cand =
+        c0 >= (uint64_t)limit || (tile + 1 < ntiles && tbase[ntiles + tile + 1] == c0);
+    if (s1 == s0 && no_cand) return;
+  }
+  U raw[kSelItems];
+  select_load<KT, U, false>(a, base, cnt, raw);
+  int64_t pos[kSelItems];  // destination record, -1: not selected
+  if (tbase == nullptr) {
+#pragma unroll
+    for (int k = 0; k < kSelItems; k++) {
+      const int e = k * kSelThreads + t;
+      pos[k] = (e < cnt && base + e < limit) ? base + e : -1;
+    }
+  } else {
+    const Xform<U> xf = select_xform<U>(a);
+    const U pv = (U)a.pv;
+    uint32_t cls = 0;  // 2 bits per slot: 1 sure, 2 candidate
+    uint32_t rk[kSelItems];
+#pragma unroll
+    for (int k = 0; k < kSelItems; k++) {
+      const bool ok = k * kSelThreads + t < cnt;
+      const U x = (U)(xf(raw[k]) >> a.psh);
+      const bool s = ok && !a.all && x < pv;
+      const bool c = ok && (a.all || x == pv);
+      const uint64_t bs = __ballot(s), bc = __ballot(c);
+      rk[k] = popc_below(s ? bs : bc);
+      cls |= (s ? 1u : c ? 2u : 0u) << (2 * k);
+      if (lane_id() == 0) {
+        wcnt[0][k * 4 + wave] = (uint32_t)__popcll(bs);
+        wcnt[1][k * 4 + wave] = (uint32_t)__popcll(bc);
+      }
+    }
+    __syncthreads();
+    if (t < 128) {  // waves 0 and 1: exclusive scans of the 64 (slot, wave) counts
+      const uint32_t v = wcnt[wave][lane_id()];
+      uint32_t inc = v;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(inc, o, 64);
+        if ((int)lane_id() >= o) inc += y;
+      }
+      wcnt[wave][lane_id()] = inc - v;
+    }
+    __syncthreads();
+    const int64_t sbase = (int64_t)tbase[tile], cbase = (int64_t)tbase[ntiles + tile];
+#pragma unroll
+    for (int k = 0; k < kSelItems; k++) {
+      const uint32_t c = (cls >> (2 * k)) & 3u;
+      const int64_t p = (c == 1 ? sbase : cbase) + wcnt[c == 1 ? 0 : 1][k * 4 + wave] + rk[k];
+      pos[k] = (c != 0 && p < limit) ? p : -1;
+    }
+  }
+  {  // the key column from the registers
+    const Col& C = desc->cols[0];
+    char* dst = C.base[BUF_OUT];
+    const uint32_t so = C.stride[BUF_OUT];
+#pragma unroll
+    for (int k = 0; k < kSelItems; k++)
+      if (pos[k] >= 0) stw<(int)sizeof(KT)>(dst + pos[k] * (int64_t)so, (uint64_t)raw[k]);
+  }
+  const int ncols = desc->ncols;
+  for (int c = 1; c < ncols; c++) {  // payload bytes are read for selected records only
+    const Col& C = desc->cols[c];
+    const uint32_t si = C.stride[BUF_IN], so = C.stride[BUF_OUT];
+    const char* src = C.base[BUF_IN] + base * (int64_t)si;
+    char* dst = C.base[BUF_OUT];
+    with_width(C.width, [&](auto W_) {
+      constexpr int W = decltype(W_)::value;
+      uint64_t v[kSelItems];
+#pragma unroll
+      for (int k = 0; k < kSelItems; k++)
+        v[k] = pos[k] >= 0 ? ldw<W>(src + (int64_t)(k * kSelThreads + t) * si) : 0;
+#pragma unroll
+      for (int k = 0; k < kSelItems; k++)
+        if (pos[k] >= 0) stw<W>(dst + pos[k] * (int64_t)so, v[k]);
+    });
+  }
+  if (idx_out) {
+#pragma unroll
+    for (int k = 0; k < kSelItems; k++)
+      if (pos[k] >= 0) gst<int64_t>(idx_out + pos[k], base + k * kSelThreads + t);
+  }
+}
+
+void launch_select_hist(int key_size, const SelectArgs& a, unsigned long long* hist,
+                        hipStream_t st) {
+  const int64_t ntiles = (a.n + kTile - 1) / kTile;
+  const int grid = (int)std::min<int64_t>(2048, ntiles);
+  if (grid <= 0) return;
+#define CALL(KT, U, CZ) select_hist_kernel<KT, U><<<grid, kSelThreads, 0, st>>>(a, ntiles, hist)
+  SRS_KEY_DISPATCH(key_size, CALL)
+#undef CALL
+}
+
+void launch_select_tally(int key_size, const SelectArgs& a, uint64_t* counts, hipStream_t st) {
+  const int64_t ntiles = (a.n + kTile - 1) / kTile;
+  if (ntiles <= 0) return;
+#define CALL(KT, U, CZ) \
+  select_tally_kernel<KT, U><<<(unsigned)ntiles, kSelThreads, 0, st>>>(a, ntiles, counts)
+  SRS_KEY_DISPATCH(key_size, CALL)
+#undef CALL
+}
+
+void launch_select_gather(int key_size, const SelectArgs& a, const SortDesc* d,
+                          const uint64_t* tbase, int64_t limit, int64_t* idx_out, hipStream_t st) {
+  const int64_t ntiles = (a.n + kTile - 1) / kTile;
+  if (ntiles <= 0) return;
+#define CALL(KT, U, CZ)                                                                 \
+  select_gather_kernel<KT, U><<<(unsigned)ntiles, kSelThreads, 0, st>>>(a, d, tbase, ntiles, \
+                                                                        limit, idx_out)
+  SRS_KEY_DISPATCH(key_size, CALL)
+#undef CALL
+}
+
 }  // namespace srs

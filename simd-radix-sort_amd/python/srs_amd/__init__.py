@@ -73,6 +73,11 @@ def lib() -> ctypes.CDLL:
     L.srs_sort_aos_device.argtypes = [i64, ctypes.c_int, ctypes.c_int, i64, vp, u32, vp, vp]
     L.srs_sort_segments_device.argtypes = [i64, ctypes.c_int, ctypes.c_int, vp, i32, vp, vp, i64,
                                            vp, i32, vp]
+    L.srs_topk_soa_device.argtypes = [i64, i64, ctypes.c_int, ctypes.c_int, vp, i32, vp, vp, vp,
+                                      vp, vp, vp]
+    L.srs_topk_aos_device.argtypes = [i64, i64, ctypes.c_int, ctypes.c_int, vp, u32, vp, vp, vp]
+    L.srs_debug_set_topk_candidates.argtypes = [i64]
+    L.srs_debug_last_topk.argtypes = [ctypes.POINTER(i64)]
     L.srs_fill_synthetic_device.argtypes = [i64, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
                                             vp, i32, vp, vp, vp]
     L.srs_key_histogram_device.argtypes = [i64, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp,
@@ -290,6 +295,70 @@ def sort_combined_device(elements, key_kind: int, up: bool = True,
                                               _stream_ptr(stream, elements.device)))
 
 
+def topk_device(keys, *payloads, k: int, up: bool = True, key_kind: int | None = None, out=None,
+                indices: bool = False, stream=None):
+    """The first min(k, n) records of the stable sort of the device columns
+    (srs_topk_soa_device): up=True the k smallest ascending, up=False the k
+    largest descending, equal keys in input order. The inputs are not
+    written. Returns (keys_out, *payloads_out[, indices]): `out` =
+    (keys_out, *payloads_out) of at least min(k, n) elements each, or new
+    tensors; with indices=True an int64 tensor of each record's input
+    position follows. Runs on keys' GPU, on `stream` or its current stream."""
+    import torch
+    _check_columns(keys, (keys,) + payloads)
+    kind = _torch_kind(keys) if key_kind is None else int(key_kind)
+    n = keys.numel()
+    kk = max(0, min(int(k), n))
+    cols = (keys,) + payloads
+    if out is None:
+        out = tuple(torch.empty(kk, dtype=c.dtype, device=keys.device) for c in cols)
+    else:
+        out = tuple(out)
+        if len(out) != len(cols):
+            raise ValueError("out must hold keys_out followed by every payload_out")
+        for o, i in zip(out, cols):
+            if not (o.is_cuda and o.device == keys.device and o.is_contiguous() and
+                    o.dim() == 1 and o.numel() >= kk and o.element_size() == i.element_size()):
+                raise ValueError("out tensors must be 1-D contiguous, on the keys' GPU, of at "
+                                 "least min(k, n) elements and of their input's element size")
+    idx = torch.empty(kk, dtype=torch.int64, device=keys.device) if indices else None
+    with _on_device(keys):
+        _check(lib().srs_topk_soa_device(
+            n, int(k), kind, int(bool(up)), keys.data_ptr(), len(payloads),
+            _ptr_array([p.data_ptr() for p in payloads]),
+            _size_array([p.element_size() for p in payloads]), out[0].data_ptr(),
+            _ptr_array([o.data_ptr() for o in out[1:]]),
+            None if idx is None else idx.data_ptr(), _stream_ptr(stream, keys.device)))
+    return out + ((idx,) if indices else ())
+
+
+def topk_combined_device(elements, key_kind: int, k: int, up: bool = True, out=None,
+                         indices: bool = False, stream=None):
+    """topk_device on a DataElement array (srs_topk_aos_device): `elements`
+    as for sort_combined_device. Returns elements_out (the first min(k, n)
+    records; `out` or a new tensor), or (elements_out, indices)."""
+    import torch
+    if not (elements.is_cuda and elements.is_contiguous()):
+        raise ValueError("elements must be a contiguous device tensor")
+    n = elements.shape[0]
+    esz = elements.numel() * elements.element_size() // max(1, n)
+    kk = max(0, min(int(k), n))
+    if out is None:
+        out = torch.empty((kk,) + tuple(elements.shape[1:]), dtype=elements.dtype,
+                          device=elements.device)
+    elif not (out.is_cuda and out.is_contiguous() and out.device == elements.device and
+              out.numel() * out.element_size() >= kk * esz):
+        raise ValueError("out must be a contiguous tensor of at least min(k, n) records on the "
+                         "same GPU")
+    idx = torch.empty(kk, dtype=torch.int64, device=elements.device) if indices else None
+    with _on_device(elements):
+        _check(lib().srs_topk_aos_device(n, int(k), int(key_kind), int(bool(up)),
+                                         elements.data_ptr(), esz, out.data_ptr(),
+                                         None if idx is None else idx.data_ptr(),
+                                         _stream_ptr(stream, elements.device)))
+    return (out, idx) if indices else out
+
+
 def fill_synthetic_device(keys, *payloads, seed: int = 42 << 32, first_index: int = 0,
                           key_kind: int | None = None, stream=None) -> None:
     """keys[i] = splitmix64(seed + first_index + i) (see srs_c_api.h);
@@ -460,6 +529,21 @@ def debug_set_super_scan(min_groups: int) -> None:
     """Scan groups from which a one-segment level takes the super-group
     column scan (srs_debug_set_super_scan; 0 = the default, 256)."""
     _check(lib().srs_debug_set_super_scan(int(min_groups)))
+
+
+def debug_set_topk_candidates(max_candidates: int) -> None:
+    """Boundary-bucket size at which the top-k select stops refining
+    (srs_debug_set_topk_candidates; 0 = the default, 2^20)."""
+    _check(lib().srs_debug_set_topk_candidates(int(max_candidates)))
+
+
+def debug_last_topk():
+    """(select passes, records handed to the finishing sort, 1 if the call
+    sorted everything) of the last top-k on the current device (synchronizes
+    the device)."""
+    c = (ctypes.c_int64 * 3)()
+    _check(lib().srs_debug_last_topk(c))
+    return int(c[0]), int(c[1]), int(c[2])
 
 
 def debug_probe_write(ptr: int, nbytes: int) -> float:
