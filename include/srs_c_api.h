@@ -198,6 +198,35 @@ int srs_topk_aos_device(int64_t num, int64_t k, int key_kind, int up,
                         const void* elements, uint32_t elem_size,
                         void* elements_out, int64_t* indices_out, void* stream);
 
+/* Row-wise top-k: srs_topk_soa_device on every row of a matrix in one call.
+ * Record i of row r of a column of width w is at base + (r * row_stride + i)
+ * * w; row_stride is in records, the same for every input column, and at
+ * least row_len (a row may start at any element: base pointers need only
+ * their element alignment). The outputs are dense: with kk = min(k, row_len),
+ * result j of row r is at r * kk + j of every *_out column. Each row's result
+ * is exactly srs_topk_soa_device's (stable, total order for floats);
+ * indices_out (may be NULL) receives positions inside the row, 0 .. row_len -
+ * 1. The inputs are never written and the records between row_len and
+ * row_stride are never selected. Checked before any device access:
+ * key_kind, payload sizes, NULL or misaligned pointers, 64 payloads with
+ * indices (as for top-k), row_stride < row_len, rows * row_stride overflowing
+ * int64, and any output over any input column (an input column spans
+ * ((rows - 1) * row_stride + row_len) * w bytes, an output rows * kk * w).
+ * rows <= 0, row_len <= 0 or k <= 0 is a no-op.
+ * Rows of at most 8192 records, and longer rows with kk <= 2048
+ * (srs_topk_rows_max_k), take ONE launch with one workgroup per row and no
+ * read-back; other shapes (and a few rows of many millions of records) run
+ * srs_topk_soa_device's select row by row, with its read-backs
+ * (DESIGN.md §12). */
+int srs_topk_rows_soa_device(int64_t rows, int64_t row_len, int64_t row_stride, int64_t k,
+                             int key_kind, int up, const void* keys, int32_t num_payloads,
+                             const void* const* payloads, const uint32_t* payload_sizes,
+                             void* keys_out, void* const* payloads_out,
+                             int64_t* indices_out, void* stream);
+/* The largest min(k, row_len) the one-launch route takes for rows longer
+ * than 8192 records (kTopkRowsMaxK). */
+int64_t srs_topk_rows_max_k(void);
+
 /* ---- multi-GPU shard primitives (top-radix-bits partition) --
  * A node-wide sort of one array spread over N GPUs: every rank histograms
  * its keys' top bits (srs_key_histogram_device), the histograms are summed
@@ -467,6 +496,19 @@ int srs_debug_set_topk_candidates(int64_t max_candidates);
  * it to prove which path an input took. info[0] = passes, info[1] = records
  * sorted, info[2] = 1 if the call took the full-sort route. */
 int srs_debug_last_topk(int64_t* info);
+
+/* Test hook, process-wide: the route srs_topk_rows_soa_device takes. -1: the
+ * library's rule; 0: resident (row_len <= 8192), 1: stream (row_len > 8192,
+ * min(k, row_len) <= srs_topk_rows_max_k()), 2: the row-by-row loop. A call
+ * whose shape the forced route cannot take returns SRS_ERR_UNSUPPORTED. */
+int srs_debug_set_topk_rows_route(int route);
+
+/* What the last row-wise top-k on the current device did (synchronizes the
+ * device): info[0] = route, info[1] = kernel launches enqueued (-1 on the
+ * loop route: not counted), info[2] = the most select (histogram) passes over
+ * the key row that any row needed (written by the kernel; 0: every row was
+ * sorted whole), info[3] = host read-backs during the call. */
+int srs_debug_last_topk_rows(int64_t* info);
 
 #ifdef __cplusplus
 }

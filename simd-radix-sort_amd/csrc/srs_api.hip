@@ -557,6 +557,10 @@ struct Workspace {
   DevBuf sel, selhist, selcnt, seldesc;
   unsigned long long* h_sel = nullptr;
   int64_t topk_info[3] = {0, 0, 0};
+  // row-wise top-k: the kernel's pass counter (one u64); what the last call did
+  DevBuf rowspass;
+  int64_t topk_rows_info[4] = {0, 0, 0, 0};
+  bool rows_pass_pending = false;  // info[2] is still in rowspass
   hipStream_t side = nullptr;  // medium sorts: the large local class's stream
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   ListCounters* h_ctr = nullptr;
@@ -591,7 +595,8 @@ struct Workspace {
                       &fallback2, &redo, &redo2, &shist, &lut, &lut_rbits, &copy, &plan, &tcount,
                       &gcount, &tbase, &gbase, &var, &sbase, &tile_seg, &group_seg, &hist, &offs,
                       &gsum, &gofs, &scan_tmp, &totals, &ctr, &prun, &ptile, &btot, &bnt, &btile,
-                      &nt_over, &gtile, &gorder, &mid, &midbar, &sel, &selhist, &selcnt, &seldesc};
+                      &nt_over, &gtile, &gorder, &mid, &midbar, &sel, &selhist, &selcnt, &seldesc,
+                      &rowspass};
     for (DevBuf* b : bufs) free_buf(*b);
     for (auto& t : small_taken) free_buf(t.second);
     if (h_sel) (void)hipHostFree(h_sel);
@@ -2392,15 +2397,11 @@ int sort_locked(Workspace* W, const Request& R, hipStream_t st) {
   return run_sort(W, R, st);
 }
 
-int topk_device(const Request& R, int64_t k, int64_t* idx_out, hipStream_t st) {
+// (under the caller's workspace lock and WsUse)
+int topk_locked(Workspace* W, const Request& R, int64_t k, int64_t* idx_out, hipStream_t st) {
   const int64_t n = R.num;
   k = std::min(k, n);
   const int ks = key_size_of(R.kind);
-  Workspace* W = nullptr;
-  WsLock lk;
-  SRS_TRY(acquire_ws(&W, &lk));
-  WsUse use;
-  SRS_TRY(use.begin(W, st));
   const bool full = n <= kLocalCap || (__int128)k * 100 > (__int128)n * topk_full_percent();
   if (k >= n && !idx_out) {  // the plain out-of-place sort
     W->topk_info[0] = 0;
@@ -2581,6 +2582,15 @@ int topk_device(const Request& R, int64_t k, int64_t* idx_out, hipStream_t st) {
   return SRS_OK;
 }
 
+int topk_device(const Request& R, int64_t k, int64_t* idx_out, hipStream_t st) {
+  Workspace* W = nullptr;
+  WsLock lk;
+  SRS_TRY(acquire_ws(&W, &lk));
+  WsUse use;
+  SRS_TRY(use.begin(W, st));
+  return topk_locked(W, R, k, idx_out, st);
+}
+
 bool ranges_overlap(const void* a, size_t an, const void* b, size_t bn) {
   const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
   return an && bn && x < y + bn && y < x + an;
@@ -2608,6 +2618,125 @@ int topk_validate(const Request& R, int64_t k, const void* out0, const int64_t* 
       if (ranges_overlap(op, ob, R.in_cols[c], (size_t)R.num * R.widths[c]))
         return fail(SRS_ERR_INVALID_ARG, "top-k outputs must not overlap the inputs");
   }
+  return SRS_OK;
+}
+
+// ---------------------------------------------------------------------------
+// row-wise top-k: the first k records of every row of a
+// matrix. Rows that fit one workgroup's registers (resident) and longer rows
+// with k <= kTopkRowsMaxK (stream) take one launch, a workgroup per row, with
+// nothing read back; everything else goes row by row through topk_locked.
+// ---------------------------------------------------------------------------
+enum { ROWS_RESIDENT = 0, ROWS_STREAM = 1, ROWS_LOOP = 2 };
+std::atomic<int> g_topk_rows_route{-1};  // srs_debug_set_topk_rows_route
+// The stream route puts one workgroup on a row, so a few very long rows leave
+// most of the chip idle while the loop's select runs each row on all of it.
+// Measured (tools/topk_rows_bench.py --sweep): the routes
+// cross at 11-16 rows of 2^20 records, 35-49 of 2^22, 116-129 of 2^24 and
+// ~350 of 2^26, i.e. near 12 * (row_len / 2^20)^0.8 rows; below that many
+// rows the loop is taken. Rows shorter than 2^20 were not measured: stream.
+constexpr int64_t kTopkRowsLoopLen = int64_t(1) << 20;
+bool topk_rows_prefers_loop(int64_t rows, int64_t row_len) {
+  if (row_len < kTopkRowsLoopLen) return false;
+  return (double)rows < 12.0 * std::pow((double)row_len / (double)kTopkRowsLoopLen, 0.8);
+}
+
+// R describes one row (R.num = row_len; the columns point at row 0).
+int topk_rows_validate(const Request& R, int64_t rows, int64_t row_stride, int64_t kk,
+                       const void* out0, const int64_t* idx_out) {
+  if (row_stride < R.num) return fail(SRS_ERR_INVALID_ARG, "row_stride < row_len");
+  int64_t cells = 0;
+  if (__builtin_mul_overflow(rows, row_stride, &cells) || cells > (INT64_MAX >> 4))
+    return fail(SRS_ERR_INVALID_ARG, "rows * row_stride overflows");
+  if (!R.in_cols[0]) return fail(SRS_ERR_INVALID_ARG, "keys is NULL");
+  if (!out0) return fail(SRS_ERR_INVALID_ARG, "keys_out is NULL");
+  for (int c = 0; c < R.ncols; c++) {
+    if (!R.in_cols[c] || !R.out_cols[c]) return fail(SRS_ERR_INVALID_ARG, "payload pointer is NULL");
+    if (((uintptr_t)R.in_cols[c] | (uintptr_t)R.out_cols[c]) % R.widths[c] != 0)
+      return fail(SRS_ERR_INVALID_ARG, "device arrays must be aligned to their element size");
+  }
+  if ((uintptr_t)idx_out % 8 != 0) return fail(SRS_ERR_INVALID_ARG, "indices_out must be 8-byte aligned");
+  const size_t in_recs = (size_t)((rows - 1) * row_stride + R.num), out_recs = (size_t)(rows * kk);
+  for (int o = 0; o <= R.ncols; o++) {
+    const void* op = o < R.ncols ? R.out_cols[o] : (const void*)idx_out;
+    const size_t ob = out_recs * (o < R.ncols ? R.widths[o] : 8);
+    if (!op) continue;
+    for (int c = 0; c < R.ncols; c++)
+      if (ranges_overlap(op, ob, R.in_cols[c], in_recs * R.widths[c]))
+        return fail(SRS_ERR_INVALID_ARG, "top-k outputs must not overlap the inputs");
+  }
+  return SRS_OK;
+}
+
+int topk_rows_device(const Request& R, int64_t rows, int64_t row_stride, int64_t k,
+                     int64_t* idx_out, hipStream_t st) {
+  const int64_t n = R.num, kk = std::min(k, n);
+  const bool can_resident = n <= kLocalCap;
+  const bool can_stream = !can_resident && kk <= kTopkRowsMaxK && n < (int64_t(1) << 31);
+  int route = g_topk_rows_route.load();
+  if (route < 0) {
+    route = can_resident ? ROWS_RESIDENT
+            : can_stream && !topk_rows_prefers_loop(rows, n) ? ROWS_STREAM
+                                                                                  : ROWS_LOOP;
+  } else if (route == ROWS_RESIDENT && !can_resident) {
+    return fail(SRS_ERR_UNSUPPORTED, "top-k rows: the resident route takes row_len <= 8192");
+  } else if (route == ROWS_STREAM && !can_stream) {
+    return fail(SRS_ERR_UNSUPPORTED,
+                "top-k rows: the stream route takes 8192 < row_len < 2^31 and min(k, row_len) <= "
+                "kTopkRowsMaxK");
+  }
+  Workspace* W = nullptr;
+  WsLock lk;
+  SRS_TRY(acquire_ws(&W, &lk));
+  WsUse use;
+  SRS_TRY(use.begin(W, st));
+  int64_t* info = W->topk_rows_info;
+  info[0] = route;
+  info[1] = info[2] = info[3] = 0;
+
+  if (route == ROWS_LOOP) {
+    // correct and slow: every row is one single-array top-k, with its select
+    // passes' read-backs (info[1]: its launches are not counted)
+    info[1] = -1;
+    for (int64_t r = 0; r < rows; r++) {
+      Request Q = R;
+      for (int c = 0; c < R.ncols; c++) {
+        Q.in_cols[c] = (char*)R.in_cols[c] + r * row_stride * (int64_t)R.widths[c];
+        Q.out_cols[c] = (char*)R.out_cols[c] + r * kk * (int64_t)R.widths[c];
+      }
+      SRS_TRY(topk_locked(W, Q, k, idx_out ? idx_out + r * kk : nullptr, st));
+      info[2] = std::max(info[2], W->topk_info[0]);
+      info[3] += W->topk_info[0];
+    }
+    W->rows_pass_pending = false;
+    return SRS_OK;
+  }
+
+  SRS_TRY(ensure(W->rowspass, sizeof(unsigned long long)));
+  HIP_TRY(hipMemsetAsync(W->rowspass.p, 0, sizeof(unsigned long long), st));
+  SortDesc kd;
+  memset(&kd, 0, sizeof kd);
+  key_masks(R.kind, R.up, kd);
+  TopkRowsArgs a;
+  memset(&a, 0, sizeof a);
+  a.rows = rows;
+  a.row_len = n;
+  a.row_stride = row_stride;
+  a.kk = kk;
+  a.ncols = R.ncols;
+  a.key_bits = kd.key_bits;
+  a.mpos = kd.mpos;
+  a.mneg = kd.mneg;
+  a.idx_out = idx_out;
+  a.max_passes = (unsigned long long*)W->rowspass.p;
+  for (int c = 0; c < R.ncols; c++)
+    a.col[c] = TopkRowsCol{(const char*)R.in_cols[c], (char*)R.out_cols[c], R.widths[c]};
+  {
+    TimedScope ts("topk_rows", (double)rows * (double)n, st);
+    HIP_TRY(launch_topk_rows(key_size_of(R.kind), a, route == ROWS_STREAM, st));
+  }
+  info[1] = 1;
+  W->rows_pass_pending = true;
   return SRS_OK;
 }
 
@@ -3374,6 +3503,23 @@ int srs_topk_soa_device(int64_t num, int64_t k, int key_kind, int up, const void
   return topk_device(R, k, indices_out, (hipStream_t)stream);
 }
 
+int srs_topk_rows_soa_device(int64_t rows, int64_t row_len, int64_t row_stride, int64_t k,
+                             int key_kind, int up, const void* keys, int32_t num_payloads,
+                             const void* const* payloads, const uint32_t* payload_sizes,
+                             void* keys_out, void* const* payloads_out, int64_t* indices_out,
+                             void* stream) {
+  Request R;
+  SRS_TRY(build_soa(R, row_len, key_kind, up, 0, (void*)keys, num_payloads,
+                    (void* const*)payloads, payload_sizes, keys_out, payloads_out));
+  if (indices_out && num_payloads > SRS_MAX_PAYLOADS - 1)
+    return fail(SRS_ERR_UNSUPPORTED,
+                "indices_out travels as one more payload column: at most 63 payload columns "
+                "with it");
+  if (rows <= 0 || row_len <= 0 || k <= 0) return SRS_OK;
+  SRS_TRY(topk_rows_validate(R, rows, row_stride, std::min(k, row_len), keys_out, indices_out));
+  return topk_rows_device(R, rows, row_stride, k, indices_out, (hipStream_t)stream);
+}
+
 int srs_topk_aos_device(int64_t num, int64_t k, int key_kind, int up, const void* elements,
                         uint32_t elem_size, void* elements_out, int64_t* indices_out,
                         void* stream) {
@@ -3711,5 +3857,29 @@ int srs_debug_last_topk(int64_t* info) {
   for (int i = 0; i < 3; i++) info[i] = W->topk_info[i];
   return SRS_OK;
 }
+
+int srs_debug_set_topk_rows_route(int route) {
+  if (route < -1 || route > ROWS_LOOP) return fail(SRS_ERR_INVALID_ARG, "route must be -1, 0, 1 or 2");
+  g_topk_rows_route.store(route);
+  return SRS_OK;
+}
+
+int srs_debug_last_topk_rows(int64_t* info) {
+  if (!info) return fail(SRS_ERR_INVALID_ARG, "info is NULL");
+  Workspace* W = nullptr;
+  WsLock lk;
+  SRS_TRY(acquire_ws(&W, &lk));
+  HIP_TRY(hipDeviceSynchronize());
+  if (W->rows_pass_pending) {
+    unsigned long long passes = 0;
+    HIP_TRY(hipMemcpy(&passes, W->rowspass.p, sizeof passes, hipMemcpyDeviceToHost));
+    W->topk_rows_info[2] = (int64_t)passes;
+    W->rows_pass_pending = false;
+  }
+  for (int i = 0; i < 4; i++) info[i] = W->topk_rows_info[i];
+  return SRS_OK;
+}
+
+int64_t srs_topk_rows_max_k(void) { return kTopkRowsMaxK; }
 
 }  // extern "C"

@@ -163,4 +163,43 @@ void launch_select_tally(int key_size, const SelectArgs& a, uint64_t* counts, hi
 void launch_select_gather(int key_size, const SelectArgs& a, const SortDesc* d,
                           const uint64_t* tbase, int64_t limit, int64_t* idx_out, hipStream_t st);
 
+// ---- row-wise top-k ----------------------------------------
+// One workgroup per row, everything decided on the device. Record i of row r
+// of a column of width w is at in + (r * row_stride + i) * w; result j of row
+// r at out + (r * kk + j) * w. col[0] is the key column.
+struct TopkRowsCol {
+  const char* in;
+  char* out;
+  uint32_t width;
+};
+struct TopkRowsArgs {
+  int64_t rows, row_len, row_stride, kk;  // kk = min(k, row_len)
+  int32_t ncols;
+  int32_t key_bits;
+  uint64_t mpos, mneg;  // SortDesc's key transform
+  // LDS slots for the selected records (a power of two >= kk): the select
+  // refines until the records below the boundary bucket and the bucket itself
+  // fit. select == 0: the whole row fits, no histogram is allocated.
+  int32_t cap;
+  int32_t select;
+  int64_t* idx_out;                 // or null
+  unsigned long long* max_passes;   // the most select passes any row took (atomicMax)
+  TopkRowsCol col[SRS_MAX_COLS];
+};
+// the most records a streamed row can select, and with it the largest kk of
+// the stream route (a row's selected set is at most its kk - 1 sure records
+// plus a boundary bucket: 2 * kTopkRowsMaxK slots always end the refinement)
+constexpr int kTopkRowsMaxK = 2048;
+constexpr int kTopkRowsStreamCap = 2 * kTopkRowsMaxK;
+// below this many selected records a further select pass costs more than the
+// LDS sort saves
+constexpr int kTopkRowsMinCap = 256;
+// rows up to this many records are sorted whole by one wave each, four rows
+// to a workgroup
+constexpr int kRowsWaveMax = 256;
+// Fills a.cap and a.select for the shape and launches. stream == false:
+// row_len <= kLocalCap, the row is held in registers; true: kk <=
+// kTopkRowsMaxK and row_len < 2^31, the row is read from memory once per pass.
+hipError_t launch_topk_rows(int key_size, TopkRowsArgs& a, bool stream, hipStream_t st);
+
 }  // namespace srs

@@ -4933,21 +4933,22 @@ __device__ __forceinline__ Xform<U> select_xform(const SelectArgs& a) {
   return xf;
 }
 
-// The tile's keys, kSelItems per thread. A full tile of a dense, 16-byte
+// The tile's keys, ITEMS per thread of NT. A full tile of a dense, 16-byte
 // aligned key column is read 16 bytes per lane (slot order then differs from
 // element order: for the order-free counts only); otherwise slot k of thread
-// t is element k * kSelThreads + t, zero past the tile's end.
-template <typename KT, typename U, bool VEC_OK>
+// t is element k * NT + t, zero past the tile's end.
+template <typename KT, typename U, bool VEC_OK, int NT = kSelThreads, int ITEMS = kSelItems>
 __device__ __forceinline__ void select_load(const SelectArgs& a, int64_t base, int cnt,
-                                            U (&raw)[kSelItems]) {
+                                            U (&raw)[ITEMS]) {
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
   constexpr int KS = (int)sizeof(KT);
   constexpr int VPL = 16 / KS;  // keys per 16-byte load
-  if (VEC_OK && cnt == kTile && a.stride == (uint32_t)KS && ((uintptr_t)a.keys & 15) == 0) {
+  if (VEC_OK && ITEMS % VPL == 0 && cnt == NT * ITEMS && a.stride == (uint32_t)KS &&
+      ((uintptr_t)a.keys & 15) == 0) {
     const char* p = a.keys + base * KS + (int64_t)threadIdx.x * 16;
 #pragma unroll
-    for (int j = 0; j < kSelItems / VPL; j++) {
-      const u32x4 v = gld<u32x4>(p + (int64_t)j * kSelThreads * 16);
+    for (int j = 0; j < ITEMS / VPL; j++) {
+      const u32x4 v = gld<u32x4>(p + (int64_t)j * NT * 16);
 #pragma unroll
       for (int i = 0; i < VPL; i++) {
         if constexpr (KS == 8) raw[j * VPL + i] = (U)((uint64_t)v[2 * i] | ((uint64_t)v[2 * i + 1] << 32));
@@ -4958,10 +4959,25 @@ __device__ __forceinline__ void select_load(const SelectArgs& a, int64_t base, i
   } else {
     const char* p = a.keys + base * (int64_t)a.stride;
 #pragma unroll
-    for (int k = 0; k < kSelItems; k++) {
-      const int e = k * kSelThreads + (int)threadIdx.x;
+    for (int k = 0; k < ITEMS; k++) {
+      const int e = k * NT + (int)threadIdx.x;
       raw[k] = e < cnt ? (U)gld<KT>(p + (int64_t)e * a.stride) : (U)0;
     }
+  }
+}
+
+// One key's digit into the LDS histogram h (`spare`: a key that does not
+// count). A wave's 64 consecutive keys often share their digit (sorted or
+// constant input; below the first pass nearly every key is outside the
+// prefix): the lanes that agree with the leading lane add once. Called by
+// whole waves.
+__device__ __forceinline__ void select_hist_add(uint32_t* h, uint32_t d, uint32_t spare) {
+  const uint32_t d0 = __builtin_amdgcn_readfirstlane(d);
+  const uint64_t same = __ballot(d == d0);
+  if (d != d0) {
+    if (d != spare) atomicAdd(&h[d], 1u);
+  } else if (lane_id() == 0 && d0 != spare) {
+    atomicAdd(&h[d0], (uint32_t)__popcll(same));
   }
 }
 
@@ -4998,16 +5014,7 @@ __global__ __launch_bounds__(kSelThreads) void select_hist_kernel(
       vor |= ok ? u : (U)0;
       vnand |= ok ? (U)~u : (U)0;
       const uint32_t d = ok ? ((uint32_t)(u >> a.shift) & mask) : kSpare;
-      // A wave's 64 consecutive keys often share their digit (sorted or
-      // constant input; below the first pass nearly every key is outside the
-      // prefix): the lanes that agree with the leading lane add once.
-      const uint32_t d0 = __builtin_amdgcn_readfirstlane(d);
-      const uint64_t same = __ballot(d == d0);
-      if (d != d0) {
-        if (d != kSpare) atomicAdd(&h[d], 1u);
-      } else if (lane_id() == 0 && d0 != kSpare) {
-        atomicAdd(&h[d0], (uint32_t)__popcll(same));
-      }
+      select_hist_add(h, d, kSpare);
     }
   }
 #pragma unroll
@@ -5194,6 +5201,365 @@ void launch_select_gather(int key_size, const SelectArgs& a, const SortDesc* d,
                                                                         limit, idx_out)
   SRS_KEY_DISPATCH(key_size, CALL)
 #undef CALL
+}
+
+// ---------------------------------------------------------------------------
+// row-wise top-k (srs_topk_rows_soa_device)
+//
+// The select of §11 with the host taken out: one workgroup owns a row, walks
+// the key's digits with an LDS histogram of the keys under the prefix found
+// so far (12 bits a pass, the next digit starting at the highest bit that
+// still varies), and stops once the records below the boundary bucket plus
+// the bucket fit its LDS slots, the bucket is wholly inside, or its keys are
+// all equal. The selected (transformed key, position) pairs are then
+// gathered into LDS in input order, sorted there by key and position (a
+// unique order: a bitonic network gives the stable result), and the first kk
+// records are written, payload bytes read by position for those only.
+// Resident rows (<= NT * kRowItems keys) are loaded once into registers;
+// streamed rows are read from memory once per pass. No workgroup reads
+// anything another one writes.
+// ---------------------------------------------------------------------------
+constexpr int kRowItems = 8;
+static_assert(kLocalThreads * kRowItems >= kLocalCap, "a resident row fits one workgroup's registers");
+
+// LDS writes of a wave made visible to its own lanes (no workgroup barrier)
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Bitonic network over the p2 (a power of two) pairs (sk[i], si[i]) in LDS,
+// ascending by key, then position; nt threads (t: this one), `sync` after
+// every step.
+template <typename U, typename Sync>
+__device__ __forceinline__ void rows_bitonic(U* sk, uint32_t* si, uint32_t p2, uint32_t t,
+                                             uint32_t nt, Sync&& sync) {
+  for (uint32_t k = 2; k <= p2; k <<= 1) {
+    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+      for (uint32_t i = t; i < p2 / 2; i += nt) {
+        const uint32_t lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo | j;
+        const U ka = sk[lo], kc = sk[hi];
+        const uint32_t ia = si[lo], ic = si[hi];
+        const bool gt = ka > kc || (ka == kc && ia > ic);
+        if (gt == ((lo & k) == 0)) {
+          sk[lo] = kc;
+          sk[hi] = ka;
+          si[lo] = ic;
+          si[hi] = ia;
+        }
+      }
+      sync();
+    }
+  }
+}
+
+// The first kk records of a row from the sorted positions si[0 .. kk): every
+// column read by position (payload bytes for the selected records only).
+template <typename KT>
+__device__ __forceinline__ void rows_write(const TopkRowsArgs& A, int64_t row, const uint32_t* si,
+                                           uint32_t t, uint32_t nt) {
+  constexpr int KS = (int)sizeof(KT);
+  const uint32_t n = (uint32_t)A.row_len, kk = (uint32_t)A.kk;
+  const int64_t in0 = row * A.row_stride, out0 = row * (int64_t)kk;
+  for (uint32_t j = t; j < kk; j += nt) {
+    const uint32_t e = si[j];
+    if (e >= n) continue;  // (a padding slot: never inside the first kk)
+    stw<KS>(A.col[0].out + (out0 + j) * KS, (uint64_t)gld<KT>(A.col[0].in + (in0 + e) * KS));
+    if (A.idx_out) gst<int64_t>(A.idx_out + out0 + j, (int64_t)e);
+  }
+  for (int c = 1; c < A.ncols; c++) {
+    const TopkRowsCol& C = A.col[c];
+    with_width(C.width, [&](auto W_) {
+      constexpr int W = decltype(W_)::value;
+      for (uint32_t j = t; j < kk; j += nt) {
+        const uint32_t e = si[j];
+        if (e < n) stw<W>(C.out + (out0 + j) * W, ldw<W>(C.in + (in0 + e) * W));
+      }
+    });
+  }
+}
+
+// Rows of at most kRowsWaveMax records: one WAVE per row, kRowsWaveThreads /
+// 64 rows to a workgroup, no workgroup barrier. The row is sorted whole in
+// the wave's LDS slab of A.cap (>= row_len, a power of two) pairs.
+constexpr int kRowsWaveThreads = 256;
+template <typename KT, typename U>
+__global__ __launch_bounds__(kRowsWaveThreads) void topk_rows_wave_kernel(const TopkRowsArgs A) {
+  constexpr int KS = (int)sizeof(KT);
+  constexpr int WPB = kRowsWaveThreads / 64;
+  extern __shared__ __attribute__((aligned(16))) unsigned char topk_rows_lds[];
+  const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
+  const int64_t row = (int64_t)blockIdx.x * WPB + wave;
+  if (row >= A.rows) return;  // (whole waves: nothing below waits for another wave)
+  const uint32_t n = (uint32_t)A.row_len, p2 = (uint32_t)A.cap;
+  U* const sk = (U*)topk_rows_lds + wave * p2;
+  uint32_t* const si = (uint32_t*)((U*)topk_rows_lds + WPB * p2) + wave * p2;
+  SelectArgs a;
+  a.key_bits = A.key_bits;
+  a.mpos = A.mpos;
+  a.mneg = A.mneg;
+  const Xform<U> xf = select_xform<U>(a);
+  const char* keys = A.col[0].in + row * A.row_stride * KS;
+  for (uint32_t e = lane; e < p2; e += 64) {
+    const bool ok = e < n;
+    sk[e] = ok ? xf((U)gld<KT>(keys + (int64_t)e * KS)) : (U)~(U)0;
+    si[e] = ok ? e : 0xffffffffu;
+  }
+  wave_lds_sync();
+  rows_bitonic(sk, si, p2, lane, 64u, [] { wave_lds_sync(); });
+  rows_write<KT>(A, row, si, lane, 64u);
+}
+
+template <typename KT, typename U, int NT, bool STREAM>
+__global__ __launch_bounds__(NT) void topk_rows_kernel(const TopkRowsArgs A) {
+  constexpr int KS = (int)sizeof(KT);
+  constexpr int NW = NT / 64;
+  constexpr int TILE = NT * kRowItems;
+  constexpr int NB = 1 << kHistMaxBits;
+  constexpr int BPT = NB / NT > 0 ? NB / NT : 1;  // histogram bins a thread sums
+  constexpr uint32_t kSpare = (uint32_t)NB;
+  static_assert(NB % NT == 0, "the bin walk gives every thread whole bins");
+  static_assert(kRowItems * NW <= NT, "one thread per (slot, wave) count");
+  extern __shared__ __attribute__((aligned(16))) unsigned char topk_rows_lds[];
+  __shared__ uint32_t scan_sh[NW + 1];
+  __shared__ uint32_t wcnt[kRowItems * NW];  // per (slot, wave): sure | candidates << 16
+  __shared__ unsigned long long bc[5];       // bucket, records below it, its size, OR, inverted AND
+  U* const sk = (U*)topk_rows_lds;                 // [cap] transformed keys of the selected records
+  uint32_t* const si = (uint32_t*)(sk + A.cap);    // [cap] their positions in the row
+  uint32_t* const h = si + A.cap;                  // [NB] (select only)
+  const int t = (int)threadIdx.x, wave = t >> 6;
+  const int kb = A.key_bits;
+  const uint64_t kmask = kb == 64 ? ~0ull : ((1ull << kb) - 1);
+  const uint32_t n = (uint32_t)A.row_len, kk = (uint32_t)A.kk, cap = (uint32_t)A.cap;
+
+  for (int64_t row = blockIdx.x; row < A.rows; row += gridDim.x) {
+    SelectArgs a;
+    a.keys = A.col[0].in + row * A.row_stride * KS;
+    a.stride = (uint32_t)KS;
+    a.n = n;
+    a.key_bits = kb;
+    a.mpos = A.mpos;
+    a.mneg = A.mneg;
+    const Xform<U> xf = select_xform<U>(a);
+    U raw[kRowItems];
+    if constexpr (!STREAM) {
+      select_load<KT, U, false, NT, kRowItems>(a, 0, (int)n, raw);
+#pragma unroll
+      for (int k = 0; k < kRowItems; k++) raw[k] = xf(raw[k]);
+    }
+
+    // ---- which records: the prefix of the boundary bucket --------------------
+    uint64_t prefix = 0;        // the fixed top bits, in place
+    int fixed = 0, top = kb;    // the next digit ends below bit `top`
+    uint32_t k_rem = kk, cand = n;  // the rank wanted inside the prefix's bucket; its size
+    bool resolved = false;      // the bucket's keys are all equal
+    uint32_t passes = 0;
+    while (A.select && !resolved && cand != k_rem && (kk - k_rem) + cand > cap) {
+      const int bits = min(kHistMaxBits, top), shift = top - bits;
+      const bool all = fixed == 0;
+      const int psh = all ? 0 : kb - fixed;
+      const U pv = all ? (U)0 : (U)(prefix >> psh);
+      const uint32_t nb = 1u << bits, mask = nb - 1;
+      for (uint32_t i = t; i < nb; i += NT) h[i] = 0;
+      if (t < 5) bc[t] = 0;
+      __syncthreads();
+      U vor = 0, vnand = 0;
+      auto count = [&](U u, bool ok) {
+        ok = ok && (all || (U)(u >> psh) == pv);
+        vor |= ok ? u : (U)0;
+        vnand |= ok ? (U)~u : (U)0;
+        select_hist_add(h, ok ? ((uint32_t)(u >> shift) & mask) : kSpare, kSpare);
+      };
+      if constexpr (STREAM) {
+        for (uint32_t base = 0; base < n; base += TILE) {
+          const int cnt = (int)min((uint32_t)TILE, n - base);
+          select_load<KT, U, true, NT, kRowItems>(a, base, cnt, raw);
+          const bool full = cnt == TILE;  // (a partial tile is always read in element order)
+#pragma unroll
+          for (int k = 0; k < kRowItems; k++) count(xf(raw[k]), full || k * NT + t < cnt);
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < kRowItems; k++) count(raw[k], (uint32_t)(k * NT + t) < n);
+      }
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) {
+        vor |= __shfl_xor(vor, o, 64);
+        vnand |= __shfl_xor(vnand, o, 64);
+      }
+      if (lane_id() == 0) {
+        atomicOr(&bc[3], (unsigned long long)vor);
+        atomicOr(&bc[4], (unsigned long long)vnand);
+      }
+      __syncthreads();
+      {  // the bucket that holds rank k_rem: a block scan over the threads' bin sums
+        uint32_t c[BPT], s = 0;
+#pragma unroll
+        for (int i = 0; i < BPT; i++) {
+          const uint32_t bin = (uint32_t)(t * BPT + i);
+          c[i] = bin < nb ? h[bin] : 0u;
+          s += c[i];
+        }
+        uint32_t tot;
+        uint32_t below = block_excl_scan<NT>(s, scan_sh, &tot);
+        if (below < k_rem && k_rem <= below + s) {
+#pragma unroll
+          for (int i = 0; i < BPT; i++) {
+            if (below + c[i] >= k_rem) {
+              bc[0] = (unsigned long long)(t * BPT + i);
+              bc[1] = below;
+              bc[2] = c[i];
+              break;
+            }
+            below += c[i];
+          }
+        }
+      }
+      __syncthreads();
+      const uint64_t b = bc[0], hor = bc[3], hnand = bc[4];
+      k_rem -= (uint32_t)bc[1];
+      cand = (uint32_t)bc[2];
+      __syncthreads();  // (bc and h are written again by the next pass)
+      passes++;
+      prefix |= b << shift;
+      fixed = kb - shift;
+      // where the bucket's parent still varies below this digit: the next
+      // digit starts at its highest varying bit, the bits between are shared
+      const uint64_t low = (1ull << shift) - 1;  // (shift <= 52)
+      const uint64_t vand = ~hnand & kmask;
+      const uint64_t var = (hor ^ vand) & low;
+      if (var == 0) {
+        resolved = true;
+        prefix |= vand & low;
+        fixed = kb;
+      } else {
+        const int hb = 63 - __builtin_clzll(var);
+        if (cand != k_rem && (kk - k_rem) + cand > cap) {
+          prefix |= vand & low & ~((2ull << hb) - 1);
+          fixed = kb - (hb + 1);
+          top = hb + 1;
+        }
+      }
+    }
+
+    // ---- the selected records into LDS, in input order -----------------------
+    // everything below the prefix, and the bucket itself (a bucket of equal
+    // keys: only its first k_rem records)
+    const bool all = fixed == 0;
+    const int psh = all ? 0 : kb - fixed;
+    const U pv = all ? (U)0 : (U)(prefix >> psh);
+    const uint32_t nsure = kk - k_rem;
+    const uint32_t climit = resolved ? k_rem : cand;
+    const uint32_t m = min(nsure + climit, cap);  // (never above cap: the stop rule)
+    uint32_t rs = 0, rc = 0;  // sure records / candidates before this tile
+    for (uint32_t base = 0; base < n; base += TILE) {
+      const int cnt = (int)min((uint32_t)TILE, n - base);
+      if constexpr (STREAM) {
+        select_load<KT, U, false, NT, kRowItems>(a, base, cnt, raw);
+#pragma unroll
+        for (int k = 0; k < kRowItems; k++) raw[k] = xf(raw[k]);
+      }
+      uint32_t cls = 0;  // 2 bits per slot: 1 sure, 2 candidate
+      uint32_t rk[kRowItems];
+#pragma unroll
+      for (int k = 0; k < kRowItems; k++) {
+        const bool ok = k * NT + t < cnt;
+        const U x = (U)(raw[k] >> psh);
+        const bool s = ok && !all && x < pv;
+        const bool c = ok && (all || x == pv);
+        const uint64_t bs = __ballot(s), bcand = __ballot(c);
+        rk[k] = popc_below(s ? bs : bcand);
+        cls |= (s ? 1u : c ? 2u : 0u) << (2 * k);
+        if (lane_id() == 0) wcnt[k * NW + wave] = (uint32_t)__popcll(bs) | ((uint32_t)__popcll(bcand) << 16);
+      }
+      __syncthreads();
+      uint32_t tot;
+      const uint32_t v = t < kRowItems * NW ? wcnt[t] : 0u;
+      const uint32_t pre = block_excl_scan<NT>(v, scan_sh, &tot);  // (a tile's counts stay below 2^16)
+      if (t < kRowItems * NW) wcnt[t] = pre;
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < kRowItems; k++) {
+        const uint32_t c = (cls >> (2 * k)) & 3u;
+        const uint32_t p = wcnt[k * NW + wave];
+        const uint32_t rank_c = rc + (p >> 16) + rk[k];
+        const uint32_t slot = c == 1 ? rs + (p & 0xffffu) + rk[k] : nsure + rank_c;
+        if ((c == 1 || (c == 2 && rank_c < climit)) && slot < m) {
+          sk[slot] = raw[k];
+          si[slot] = base + (uint32_t)(k * NT + t);
+        }
+      }
+      rs += tot & 0xffffu;
+      rc += tot >> 16;
+      __syncthreads();  // (wcnt is written again by the next tile)
+      if (rs >= nsure && rc >= climit) break;
+    }
+
+    // ---- sort by (key, position), padded to a power of two ---------------------
+    uint32_t p2 = 1;
+    while (p2 < m) p2 <<= 1;
+    for (uint32_t i = m + t; i < p2; i += NT) {
+      sk[i] = (U)~(U)0;
+      si[i] = 0xffffffffu;
+    }
+    __syncthreads();
+    rows_bitonic(sk, si, p2, (uint32_t)t, (uint32_t)NT, [] { __syncthreads(); });
+
+    // ---- the first kk records, every column read by position -----------------
+    rows_write<KT>(A, row, si, (uint32_t)t, (uint32_t)NT);
+    if (t == 0 && passes > (uint32_t)gld<unsigned long long>(A.max_passes))
+      atomicMax(A.max_passes, (unsigned long long)passes);
+    __syncthreads();  // (the LDS slots are the next row's)
+  }
+}
+
+size_t topk_rows_lds_bytes(int key_size, const TopkRowsArgs& a) {
+  const size_t u = key_size == 8 ? 8 : 4;
+  return (size_t)a.cap * (u + 4) + (a.select ? sizeof(uint32_t) << kHistMaxBits : 0);
+}
+
+hipError_t launch_topk_rows(int key_size, TopkRowsArgs& a, bool stream, hipStream_t st) {
+  // the stop rule's capacity: rows up to max(2 kk, kTopkRowsMinCap) records
+  // are sorted whole; longer ones are refined down to that many slots
+  int64_t fit = std::max<int64_t>(2 * a.kk, kTopkRowsMinCap);
+  const int64_t route_cap = stream ? kTopkRowsStreamCap : kLocalCap;
+  a.select = a.row_len > fit;
+  int64_t want = std::min(a.select ? fit : a.row_len, route_cap), cap = 2;
+  while (cap < want) cap <<= 1;
+  a.cap = (int32_t)cap;
+  hipError_t err = hipSuccess;
+  constexpr int64_t kWaveRows = kRowsWaveThreads / 64;
+  if (!stream && a.row_len <= kRowsWaveMax && (a.rows + kWaveRows - 1) / kWaveRows <= 0x7fffffff) {
+    const unsigned grid = (unsigned)((a.rows + kWaveRows - 1) / kWaveRows);
+    const size_t lds = kWaveRows * (topk_rows_lds_bytes(key_size, a));  // (select == 0 here)
+#define CALL(KT, U, CZ) topk_rows_wave_kernel<KT, U><<<grid, kRowsWaveThreads, lds, st>>>(a)
+    SRS_KEY_DISPATCH(key_size, CALL)
+#undef CALL
+    return hipGetLastError();
+  }
+  const size_t lds = topk_rows_lds_bytes(key_size, a);
+  const unsigned grid = (unsigned)std::min<int64_t>(a.rows, 0x7fffffff);
+#define ROWS_GO(KT, U, NT, STREAM)                                                       \
+  do {                                                                                   \
+    auto kern = topk_rows_kernel<KT, U, NT, STREAM>;                                     \
+    if (lds > 48 * 1024)                                                                 \
+      err = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                (int)lds);                                               \
+    if (err == hipSuccess) kern<<<grid, NT, lds, st>>>(a);                               \
+  } while (0)
+#define CALL(KT, U, CZ)                                                 \
+  do {                                                                  \
+    if (stream) ROWS_GO(KT, U, 1024, true);                             \
+    else if (a.row_len <= 128 * kRowItems) ROWS_GO(KT, U, 128, false);  \
+    else if (a.row_len <= 256 * kRowItems) ROWS_GO(KT, U, 256, false);  \
+    else if (a.row_len <= 512 * kRowItems) ROWS_GO(KT, U, 512, false);  \
+    else ROWS_GO(KT, U, 1024, false);                                   \
+  } while (0)
+  SRS_KEY_DISPATCH(key_size, CALL)
+#undef CALL
+#undef ROWS_GO
+  return err != hipSuccess ? err : hipGetLastError();
 }
 
 }  // namespace srs

@@ -78,6 +78,11 @@ def lib() -> ctypes.CDLL:
     L.srs_topk_aos_device.argtypes = [i64, i64, ctypes.c_int, ctypes.c_int, vp, u32, vp, vp, vp]
     L.srs_debug_set_topk_candidates.argtypes = [i64]
     L.srs_debug_last_topk.argtypes = [ctypes.POINTER(i64)]
+    L.srs_topk_rows_soa_device.argtypes = [i64, i64, i64, i64, ctypes.c_int, ctypes.c_int, vp, i32,
+                                           vp, vp, vp, vp, vp, vp]
+    L.srs_topk_rows_max_k.restype = i64
+    L.srs_debug_set_topk_rows_route.argtypes = [ctypes.c_int]
+    L.srs_debug_last_topk_rows.argtypes = [ctypes.POINTER(i64)]
     L.srs_fill_synthetic_device.argtypes = [i64, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
                                             vp, i32, vp, vp, vp]
     L.srs_key_histogram_device.argtypes = [i64, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp,
@@ -332,6 +337,60 @@ def topk_device(keys, *payloads, k: int, up: bool = True, key_kind: int | None =
     return out + ((idx,) if indices else ())
 
 
+# the largest min(k, row_len) topk_rows_device's one-launch route takes for
+# rows longer than 8192 records (kTopkRowsMaxK; srs_topk_rows_max_k())
+TOPK_ROWS_MAX_K = 2048
+TOPK_ROWS_RESIDENT, TOPK_ROWS_STREAM, TOPK_ROWS_LOOP = 0, 1, 2
+
+
+def topk_rows_device(keys, *payloads, k: int, up: bool = True, key_kind: int | None = None,
+                     out=None, indices: bool = False, stream=None):
+    """topk_device on every row of a matrix in one call
+    (srs_topk_rows_soa_device). The inputs are 2-D device tensors of equal
+    shape (rows, row_len) with stride(1) == 1 and equal stride(0) >= row_len:
+    a sliced view m[:, :L] works without a copy. Returns (keys_out,
+    *payloads_out[, indices]) of shape (rows, min(k, row_len)): `out` =
+    (keys_out, *payloads_out), contiguous, or new tensors; indices=True adds
+    an int64 tensor of each record's position inside its row."""
+    import torch
+    cols = (keys,) + payloads
+    if keys.dim() != 2:
+        raise ValueError("keys must be a 2-D tensor (rows, row_len)")
+    rows, n = keys.shape
+    # (a matrix of one row or of one column may report any stride for that dim)
+    stride = keys.stride(0) if rows > 1 else max(n, 1)
+    for t in cols:
+        if not (t.is_cuda and t.dim() == 2 and tuple(t.shape) == (rows, n)):
+            raise ValueError("columns must be 2-D device tensors of equal shape")
+        if t.device != keys.device:
+            raise ValueError(f"columns must all be on {keys.device} (got {t.device})")
+        if (n > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) != stride) or stride < n:
+            raise ValueError("columns must have stride(1) == 1 and equal stride(0) >= row_len")
+    kind = _torch_kind(keys) if key_kind is None else int(key_kind)
+    kk = max(0, min(int(k), n))
+    if out is None:
+        out = tuple(torch.empty((rows, kk), dtype=c.dtype, device=keys.device) for c in cols)
+    else:
+        out = tuple(out)
+        if len(out) != len(cols):
+            raise ValueError("out must hold keys_out followed by every payload_out")
+        for o, i in zip(out, cols):
+            if not (o.is_cuda and o.device == keys.device and o.is_contiguous() and
+                    o.numel() >= rows * kk and o.element_size() == i.element_size()):
+                raise ValueError("out tensors must be contiguous, on the keys' GPU, of at least "
+                                 "rows * min(k, row_len) elements and of their input's element "
+                                 "size")
+    idx = torch.empty((rows, kk), dtype=torch.int64, device=keys.device) if indices else None
+    with _on_device(keys):
+        _check(lib().srs_topk_rows_soa_device(
+            rows, n, stride, int(k), kind, int(bool(up)), keys.data_ptr(), len(payloads),
+            _ptr_array([p.data_ptr() for p in payloads]),
+            _size_array([p.element_size() for p in payloads]), out[0].data_ptr(),
+            _ptr_array([o.data_ptr() for o in out[1:]]),
+            None if idx is None else idx.data_ptr(), _stream_ptr(stream, keys.device)))
+    return out + ((idx,) if indices else ())
+
+
 def topk_combined_device(elements, key_kind: int, k: int, up: bool = True, out=None,
                          indices: bool = False, stream=None):
     """topk_device on a DataElement array (srs_topk_aos_device): `elements`
@@ -544,6 +603,21 @@ def debug_last_topk():
     c = (ctypes.c_int64 * 3)()
     _check(lib().srs_debug_last_topk(c))
     return int(c[0]), int(c[1]), int(c[2])
+
+
+def debug_set_topk_rows_route(route: int) -> None:
+    """Route of topk_rows_device, process-wide (srs_debug_set_topk_rows_route):
+    -1 the library's rule, TOPK_ROWS_RESIDENT / _STREAM / _LOOP force one."""
+    _check(lib().srs_debug_set_topk_rows_route(int(route)))
+
+
+def debug_last_topk_rows():
+    """(route, kernel launches or -1 on the loop route, most select passes
+    any row took, host read-backs) of the last topk_rows_device on the
+    current device (synchronizes the device)."""
+    c = (ctypes.c_int64 * 4)()
+    _check(lib().srs_debug_last_topk_rows(c))
+    return tuple(int(x) for x in c)
 
 
 def debug_probe_write(ptr: int, nbytes: int) -> float:
