@@ -314,6 +314,27 @@ void top_k_rows(void* stream, const SortIndex k, const SortIndex rows, const Sor
                 "device::top_k_rows");
 }
 
+// sort_rows: every row of a matrix sorted in one call, out of place
+// (srs_sort_rows_soa_device). Record i of row r of every input array is at
+// [r * row_stride + i] (row_stride >= row_len, in records); record j of row
+// r's stable sort at [r * row_len + j] of keys_out and of every payload_out.
+template <bool Up = true, typename K, typename... Ps>
+void sort_rows(void* stream, const SortIndex rows, const SortIndex row_len,
+               const SortIndex row_stride, const K* const keys, K* const keys_out,
+               std::pair<const Ps*, Ps*>... payloads) {
+  static_assert(detail::key_kind<K>() >= 0, "unsupported key type");
+  static_assert((detail::valid_payload<Ps> && ...), "payload sizes must be 1, 2, 4 or 8");
+  static_assert(sizeof...(Ps) <= SRS_MAX_PAYLOADS, "too many payload arrays");
+  const void* pays[sizeof...(Ps) + 1] = {(const void*)payloads.first..., nullptr};
+  void* pays_out[sizeof...(Ps) + 1] = {(void*)payloads.second..., nullptr};
+  uint32_t sizes[sizeof...(Ps) + 1] = {(uint32_t)sizeof(Ps)..., 0};
+  detail::check(srs_sort_rows_soa_device((int64_t)rows, (int64_t)row_len, (int64_t)row_stride,
+                                         detail::key_kind<K>(), Up ? 1 : 0, (const void*)keys,
+                                         (int32_t)sizeof...(Ps), pays, sizes, (void*)keys_out,
+                                         pays_out, nullptr, stream),
+                "device::sort_rows");
+}
+
 }  // namespace device
 }  // namespace radix_sort
 }  // namespace simd_sort

@@ -227,6 +227,34 @@ int srs_topk_rows_soa_device(int64_t rows, int64_t row_len, int64_t row_stride, 
  * than 8192 records (kTopkRowsMaxK). */
 int64_t srs_topk_rows_max_k(void);
 
+/* Row-wise sort: every row of a matrix sorted in one call, out of place.
+ * Addressing is srs_topk_rows_soa_device's: record i of row r of a column of
+ * width w is at base + (r * row_stride + i) * w, row_stride in records, the
+ * same for every input column and at least row_len. The outputs are dense:
+ * record j of row r is at r * row_len + j of every *_out column. Each row's
+ * result is the stable sort by transformed key (equal keys keep their input
+ * order; floats in the total order at every size, -0.0 before +0.0; NaN keys
+ * are outside the contract; up == 0 reverses the key order), bit-equal to
+ * srs_topk_rows_soa_device with k = row_len wherever that call runs in one
+ * launch. indices_out (may be NULL) receives positions inside the row; it
+ * travels as one more 8-byte column, so 64 payload columns with indices
+ * return SRS_ERR_UNSUPPORTED. The inputs are never written. There is no
+ * in-place form: every output must be clear of every input column.
+ * Checked before any device access, exactly as for row-wise top-k with k =
+ * row_len: key_kind, payload sizes, NULL or misaligned pointers, row_stride <
+ * row_len, rows * row_stride overflowing int64, and any output (indices
+ * included) over any input column. rows <= 0 or row_len <= 0 is a no-op;
+ * row_len == 1 copies the rows (and writes index 0).
+ * Rows of up to 8192 records take no host read-back: one launch with a
+ * workgroup per row (short rows), or the sort's LDS pass over a device-built
+ * list of one segment per row. Longer rows run the sort's global levels
+ * breadth-first over all rows, with a level's read-backs. */
+int srs_sort_rows_soa_device(int64_t rows, int64_t row_len, int64_t row_stride,
+                             int key_kind, int up, const void* keys, int32_t num_payloads,
+                             const void* const* payloads, const uint32_t* payload_sizes,
+                             void* keys_out, void* const* payloads_out,
+                             int64_t* indices_out, void* stream);
+
 /* ---- multi-GPU shard primitives (top-radix-bits partition) --
  * A node-wide sort of one array spread over N GPUs: every rank histograms
  * its keys' top bits (srs_key_histogram_device), the histograms are summed
@@ -509,6 +537,19 @@ int srs_debug_set_topk_rows_route(int route);
  * the key row that any row needed (written by the kernel; 0: every row was
  * sorted whole), info[3] = host read-backs during the call. */
 int srs_debug_last_topk_rows(int64_t* info);
+
+/* Test hook, process-wide: the route srs_sort_rows_soa_device takes. -1: the
+ * library's rule; 0: the rows kernel (row_len <= 8192), 1: the local lists
+ * (2 <= row_len <= 8192), 2: the global levels (row_len > 8192). A call whose
+ * shape the forced route cannot take returns SRS_ERR_UNSUPPORTED. Needs no
+ * device. */
+int srs_debug_set_sort_rows_route(int route);
+
+/* What the last row-wise sort on the current device did (host state only: no
+ * synchronization): info[0] = route, info[1] = kernel launches enqueued (-1:
+ * not counted), info[2] = host read-backs during the call, info[3] = 1 if the
+ * prepare pass ran (strided rows or an index column made dense). */
+int srs_debug_last_sort_rows(int64_t* info);
 
 #ifdef __cplusplus
 }

@@ -561,6 +561,10 @@ struct Workspace {
   DevBuf rowspass;
   int64_t topk_rows_info[4] = {0, 0, 0, 0};
   bool rows_pass_pending = false;  // info[2] is still in rowspass
+  // row-wise sort: the rows kernel's pass counter (unused, its own word so
+  // that the top-k hook's stays that call's); what the last call did
+  DevBuf sortrowspass;
+  int64_t sort_rows_info[4] = {0, 0, 0, 0};
   hipStream_t side = nullptr;  // medium sorts: the large local class's stream
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   ListCounters* h_ctr = nullptr;
@@ -596,7 +600,7 @@ struct Workspace {
                       &gcount, &tbase, &gbase, &var, &sbase, &tile_seg, &group_seg, &hist, &offs,
                       &gsum, &gofs, &scan_tmp, &totals, &ctr, &prun, &ptile, &btot, &bnt, &btile,
                       &nt_over, &gtile, &gorder, &mid, &midbar, &sel, &selhist, &selcnt, &seldesc,
-                      &rowspass};
+                      &rowspass, &sortrowspass};
     for (DevBuf* b : bufs) free_buf(*b);
     for (auto& t : small_taken) free_buf(t.second);
     if (h_sel) (void)hipHostFree(h_sel);
@@ -1759,6 +1763,10 @@ int wait_mid_flag(const MidFlag* f, unsigned long long seq, hipStream_t st) {
   return SRS_OK;
 }
 
+int run_lists_tail(Workspace* W, const Request& R, const SortDesc& d, const SortDesc* d_desc,
+                   int64_t n_local, int64_t n_local2, int64_t n_copy, bool aos_cols,
+                   hipStream_t st);
+
 int run_sort(Workspace* W, const Request& R, hipStream_t st) {
   if (R.nsegs == 0 && R.num <= kLocalCap) return run_small(W, R, st);
   {
@@ -2106,10 +2114,20 @@ int run_sort(Workspace* W, const Request& R, hipStream_t st) {
     if (++level > 80) return fail(SRS_ERR_INTERNAL, "level limit exceeded");
     SRS_TRY(run_level(W, ksl, d_desc, S, 0, false, st));
   }
-  n_local = S.n_local;
-  n_local2 = S.n_local2;
-  n_copy = S.n_copy;
+  return run_lists_tail(W, R, d, d_desc, S.n_local, S.n_local2, S.n_copy, aos_cols, st);
+}
 
+// The end of every sort that went through the work lists: the LDS chain over
+// the two local lists (W->local: n_local segments of up to kLocalCapSmall
+// records, W->local2: n_local2 of up to kLocalCap), then the copy list home.
+// d is the descriptor d_desc holds; R.num the records of the whole call.
+int run_lists_tail(Workspace* W, const Request& R, const SortDesc& d, const SortDesc* d_desc,
+                   int64_t n_local, int64_t n_local2, int64_t n_copy, bool aos_cols,
+                   hipStream_t st) {
+  const int ks = key_size_of(R.kind);
+  const int ksl = ks | (d.canon_zero ? SRS_KS_CANON : 0);
+  const int64_t n = R.num;
+  ListCounters* d_ctr = (ListCounters*)W->ctr.p;
   if (n_local + n_local2 > 0) {
     note_elems("local", (double)W->h_ctr->local_elems);
     TimedScope ts("local", (double)0, st);
@@ -2642,8 +2660,10 @@ bool topk_rows_prefers_loop(int64_t rows, int64_t row_len) {
 }
 
 // R describes one row (R.num = row_len; the columns point at row 0).
+// (what: the caller's name for its outputs in the overlap message; the
+// row-wise sort validates through this too, with kk = row_len)
 int topk_rows_validate(const Request& R, int64_t rows, int64_t row_stride, int64_t kk,
-                       const void* out0, const int64_t* idx_out) {
+                       const void* out0, const int64_t* idx_out, const char* what = "top-k") {
   if (row_stride < R.num) return fail(SRS_ERR_INVALID_ARG, "row_stride < row_len");
   int64_t cells = 0;
   if (__builtin_mul_overflow(rows, row_stride, &cells) || cells > (INT64_MAX >> 4))
@@ -2663,7 +2683,39 @@ int topk_rows_validate(const Request& R, int64_t rows, int64_t row_stride, int64
     if (!op) continue;
     for (int c = 0; c < R.ncols; c++)
       if (ranges_overlap(op, ob, R.in_cols[c], in_recs * R.widths[c]))
-        return fail(SRS_ERR_INVALID_ARG, "top-k outputs must not overlap the inputs");
+        return fail(SRS_ERR_INVALID_ARG,
+                    std::string(what) + " outputs must not overlap the inputs");
+  }
+  return SRS_OK;
+}
+
+// The one-launch routes' kernel (launch_topk_rows): the first kk records of
+// every row's sorted order, kk <= row_len (kk == row_len: the rows sorted
+// whole). pass: the buffer of the kernel's pass counter.
+int launch_rows_kernel(DevBuf& pass, const Request& R, int64_t rows, int64_t row_stride,
+                       int64_t kk, int64_t* idx_out, bool stream, hipStream_t st) {
+  SRS_TRY(ensure(pass, sizeof(unsigned long long)));
+  HIP_TRY(hipMemsetAsync(pass.p, 0, sizeof(unsigned long long), st));
+  SortDesc kd;
+  memset(&kd, 0, sizeof kd);
+  key_masks(R.kind, R.up, kd);
+  TopkRowsArgs a;
+  memset(&a, 0, sizeof a);
+  a.rows = rows;
+  a.row_len = R.num;
+  a.row_stride = row_stride;
+  a.kk = kk;
+  a.ncols = R.ncols;
+  a.key_bits = kd.key_bits;
+  a.mpos = kd.mpos;
+  a.mneg = kd.mneg;
+  a.idx_out = idx_out;
+  a.max_passes = (unsigned long long*)pass.p;
+  for (int c = 0; c < R.ncols; c++)
+    a.col[c] = TopkRowsCol{(const char*)R.in_cols[c], (char*)R.out_cols[c], R.widths[c]};
+  {
+    TimedScope ts("topk_rows", (double)rows * (double)R.num, st);
+    HIP_TRY(launch_topk_rows(key_size_of(R.kind), a, stream, st));
   }
   return SRS_OK;
 }
@@ -2712,32 +2764,163 @@ int topk_rows_device(const Request& R, int64_t rows, int64_t row_stride, int64_t
     return SRS_OK;
   }
 
-  SRS_TRY(ensure(W->rowspass, sizeof(unsigned long long)));
-  HIP_TRY(hipMemsetAsync(W->rowspass.p, 0, sizeof(unsigned long long), st));
-  SortDesc kd;
-  memset(&kd, 0, sizeof kd);
-  key_masks(R.kind, R.up, kd);
-  TopkRowsArgs a;
-  memset(&a, 0, sizeof a);
-  a.rows = rows;
-  a.row_len = n;
-  a.row_stride = row_stride;
-  a.kk = kk;
-  a.ncols = R.ncols;
-  a.key_bits = kd.key_bits;
-  a.mpos = kd.mpos;
-  a.mneg = kd.mneg;
-  a.idx_out = idx_out;
-  a.max_passes = (unsigned long long*)W->rowspass.p;
-  for (int c = 0; c < R.ncols; c++)
-    a.col[c] = TopkRowsCol{(const char*)R.in_cols[c], (char*)R.out_cols[c], R.widths[c]};
-  {
-    TimedScope ts("topk_rows", (double)rows * (double)n, st);
-    HIP_TRY(launch_topk_rows(key_size_of(R.kind), a, route == ROWS_STREAM, st));
-  }
+  SRS_TRY(launch_rows_kernel(W->rowspass, R, rows, row_stride, kk, idx_out, route == ROWS_STREAM,
+                             st));
   info[1] = 1;
   W->rows_pass_pending = true;
   return SRS_OK;
+}
+
+// ---------------------------------------------------------------------------
+// row-wise sort: every row of a matrix sorted, out of place.
+// Route 0 is the rows kernel above with kk = row_len; routes 1 and 2 make the
+// rows segments of the sort's work lists on the device (launch_rows_segs) and
+// run the sort's own LDS chain / global levels over them.
+// ---------------------------------------------------------------------------
+enum { SORT_ROWS_KERNEL = 0, SORT_ROWS_LOCAL = 1, SORT_ROWS_LEVELS = 2 };
+std::atomic<int> g_sort_rows_route{-1};  // srs_debug_set_sort_rows_route
+// Rows of 257 .. kLocalCap records: the rows kernel below this length, the
+// local lists from it. Measured at 2^26 records (tools/sort_rows_bench.py
+// --sweep): the rows kernel sorts a row padded to a power of
+// two and wins at 1024 records and below on every column set; from 1025 the
+// chain's direct kernel (a 4- or 8-byte key and one 8-byte payload, no index
+// column) wins at every length measured, 1.13x at 1025 to 3.2x at 8192. The
+// chain's general kernel, which every other column set takes, wins once the
+// rows kernel pads past 4096 records (2.1x at 4097) but loses 1.5-2.3x at
+// 1152-2048: those sets cross at kSortRowsLocalMinGeneral.
+constexpr int64_t kSortRowsLocalMin = 1025;
+constexpr int64_t kSortRowsLocalMinGeneral = kLocalCapSmall + 1;
+int64_t sort_rows_local_min(const Request& R, bool with_indices) {
+  const int ks = key_size_of(R.kind);
+  const bool direct = !with_indices && R.ncols == 2 && R.widths[1] == 8 && (ks == 4 || ks == 8);
+  return direct ? kSortRowsLocalMin : kSortRowsLocalMinGeneral;
+}
+
+// Routes 1 and 2. Q is the whole matrix as one request of dense columns
+// (Q.num = rows * row_len; the index column, when asked for, is its last
+// payload): in place on the outputs after the prepare pass (IN aliases OUT,
+// the segments start in OUT), or out of place from the caller's dense input
+// (the segments start in IN). *readbacks: host waits of the levels.
+int sort_rows_lists(Workspace* W, const Request& Q, int64_t rows, int64_t row_len,
+                    int64_t* readbacks, hipStream_t st) {
+  W->last_small = false;
+  const int ks = key_size_of(Q.kind);
+  const int64_t n = Q.num;
+  const bool inplace = is_inplace(Q);
+  const bool levels = row_len > kLocalCap;
+  SortDesc d;
+  memset(&d, 0, sizeof d);
+  key_masks(Q.kind, Q.up, d);  // (threshold 0: canon_zero and leaf_skip stay 0)
+  // the levels scatter through TMP; the LDS chain alone touches IN and OUT only
+  size_t tmp_bytes = 0;
+  std::vector<size_t> tmp_off;
+  for (int c = 0; c < Q.ncols; c++) {
+    tmp_off.push_back(tmp_bytes);
+    tmp_bytes += align_up((size_t)n * Q.widths[c], 256);
+  }
+  char* tmp = nullptr;
+  if (levels) {
+    SRS_TRY(ensure(W->tmp, tmp_bytes, ws_alloc_mode(), true));
+    tmp = (char*)W->tmp.p;
+  }
+  set_columns(Q, d, tmp, nullptr, false, 0, tmp_off.data(), inplace);
+  d.stamp_acc = g_stamp_acc;
+  d.lb_status = g_lb_status;
+  d.lb_err = g_lb_err;
+  SRS_TRY(ensure(W->desc, sizeof(SortDesc)));
+  SortDesc* d_desc = (SortDesc*)W->desc.p;
+
+  // ---- the lists: one segment per row, all in one list ----------------------
+  const int cls = levels ? 2 : row_len > kLocalCapSmall ? 1 : 0;
+  const size_t cap = (size_t)std::max<int64_t>(1024, rows) * sizeof(Seg);
+  SRS_TRY(ensure(W->big[0], cls == 2 ? cap : 1024 * sizeof(Seg)));
+  SRS_TRY(ensure(W->big[1], 1024 * sizeof(Seg)));
+  SRS_TRY(ensure(W->local, cls == 0 ? cap : 1024 * sizeof(Seg)));
+  SRS_TRY(ensure(W->local2, cls == 1 ? cap : 1024 * sizeof(Seg)));
+  SRS_TRY(ensure(W->copy, 1024 * sizeof(Seg)));
+  SRS_TRY(ensure(W->ctr, sizeof(ListCounters)));
+  SRS_TRY(ensure(W->totals, 4 * sizeof(uint64_t)));
+  ListCounters* d_ctr = (ListCounters*)W->ctr.p;
+  Seg* list = (Seg*)(cls == 2 ? W->big[0].p : cls == 1 ? W->local2.p : W->local.p);
+  launch_set_desc(d, d_desc, st);
+  HIP_TRY(launch_rows_segs(list, rows, row_len, d.key_bits, inplace ? BUF_OUT : BUF_IN, cls, d_ctr,
+                           st));
+  W->h_ctr->local_elems = levels ? 0 : (uint64_t)n;
+
+  LevelState S{cls == 2 ? rows : 0, cls == 0 ? rows : 0, cls == 1 ? rows : 0, 0, 0, d.ncols,
+               d.tmp2};
+  S.pair_tiles = pair_tiles_mode(d, ks, false);
+  if (S.nbig == 1) S.known_len = row_len;
+  int level = 0;
+  while (S.nbig > 0) {
+    if (++level > 80) return fail(SRS_ERR_INTERNAL, "level limit exceeded");
+    *readbacks += (S.nbig == 1 && S.known_len >= 0) ? 1 : 2;  // (totals, counters)
+    SRS_TRY(run_level(W, ks, d_desc, S, 0, false, st));
+  }
+  return run_lists_tail(W, Q, d, d_desc, S.n_local, S.n_local2, S.n_copy, false, st);
+}
+
+// R describes one row (R.num = row_len; the columns point at row 0).
+int sort_rows_device(const Request& R, int64_t rows, int64_t row_stride, int64_t* idx_out,
+                     hipStream_t st) {
+  const int64_t len = R.num;
+  int route = g_sort_rows_route.load();
+  if (route < 0) {
+    route = len > kLocalCap ? SORT_ROWS_LEVELS
+            : len <= kRowsWaveMax || len < sort_rows_local_min(R, idx_out != nullptr)
+                ? SORT_ROWS_KERNEL
+                : SORT_ROWS_LOCAL;
+  } else if (route == SORT_ROWS_KERNEL && len > kLocalCap) {
+    return fail(SRS_ERR_UNSUPPORTED, "sort rows: the rows kernel takes row_len <= 8192");
+  } else if (route == SORT_ROWS_LOCAL && (len < 2 || len > kLocalCap)) {
+    return fail(SRS_ERR_UNSUPPORTED, "sort rows: the local lists take 2 <= row_len <= 8192");
+  } else if (route == SORT_ROWS_LEVELS && len <= kLocalCap) {
+    return fail(SRS_ERR_UNSUPPORTED, "sort rows: the levels take row_len > 8192");
+  }
+  Workspace* W = nullptr;
+  WsLock lk;
+  SRS_TRY(acquire_ws(&W, &lk));
+  WsUse use;
+  SRS_TRY(use.begin(W, st));
+  int64_t* info = W->sort_rows_info;
+  info[0] = route;
+  info[1] = info[2] = info[3] = 0;
+
+  if (route == SORT_ROWS_KERNEL) {
+    SRS_TRY(launch_rows_kernel(W->sortrowspass, R, rows, row_stride, len, idx_out, false, st));
+    info[1] = 1;
+    return SRS_OK;
+  }
+
+  info[1] = -1;  // (the chain's launches are not counted)
+  Request Q = R;
+  Q.num = rows * len;
+  const bool prepare = row_stride != len || idx_out != nullptr;
+  if (prepare) {
+    // strided rows and the index column land dense in the outputs, which are
+    // then sorted in place (no workspace column, and the
+    // in-place segment lists are the ones srs_sort_segments_device runs)
+    RowsPrepareArgs a;
+    memset(&a, 0, sizeof a);
+    a.rows = rows;
+    a.row_len = len;
+    a.row_stride = row_stride;
+    a.ncols = R.ncols;
+    a.idx_out = idx_out;
+    for (int c = 0; c < R.ncols; c++)
+      a.col[c] = TopkRowsCol{(const char*)R.in_cols[c], (char*)R.out_cols[c], R.widths[c]};
+    {
+      TimedScope ts("rows_prepare", (double)Q.num, st);
+      HIP_TRY(launch_rows_prepare(a, st));
+    }
+    info[3] = 1;
+    for (int c = 0; c < Q.ncols; c++) Q.in_cols[c] = Q.out_cols[c];
+    if (idx_out) {
+      Q.in_cols[Q.ncols] = Q.out_cols[Q.ncols] = idx_out;
+      Q.widths[Q.ncols++] = 8;
+    }
+  }
+  return sort_rows_lists(W, Q, rows, len, &info[2], st);
 }
 
 // ---------------------------------------------------------------------------
@@ -3520,6 +3703,23 @@ int srs_topk_rows_soa_device(int64_t rows, int64_t row_len, int64_t row_stride, 
   return topk_rows_device(R, rows, row_stride, k, indices_out, (hipStream_t)stream);
 }
 
+int srs_sort_rows_soa_device(int64_t rows, int64_t row_len, int64_t row_stride, int key_kind,
+                             int up, const void* keys, int32_t num_payloads,
+                             const void* const* payloads, const uint32_t* payload_sizes,
+                             void* keys_out, void* const* payloads_out, int64_t* indices_out,
+                             void* stream) {
+  Request R;
+  SRS_TRY(build_soa(R, row_len, key_kind, up, 0, (void*)keys, num_payloads,
+                    (void* const*)payloads, payload_sizes, keys_out, payloads_out));
+  if (indices_out && num_payloads > SRS_MAX_PAYLOADS - 1)
+    return fail(SRS_ERR_UNSUPPORTED,
+                "indices_out travels as one more payload column: at most 63 payload columns "
+                "with it");
+  if (rows <= 0 || row_len <= 0) return SRS_OK;
+  SRS_TRY(topk_rows_validate(R, rows, row_stride, row_len, keys_out, indices_out, "sort rows"));
+  return sort_rows_device(R, rows, row_stride, indices_out, (hipStream_t)stream);
+}
+
 int srs_topk_aos_device(int64_t num, int64_t k, int key_kind, int up, const void* elements,
                         uint32_t elem_size, void* elements_out, int64_t* indices_out,
                         void* stream) {
@@ -3881,5 +4081,21 @@ int srs_debug_last_topk_rows(int64_t* info) {
 }
 
 int64_t srs_topk_rows_max_k(void) { return kTopkRowsMaxK; }
+
+int srs_debug_set_sort_rows_route(int route) {
+  if (route < -1 || route > SORT_ROWS_LEVELS)
+    return fail(SRS_ERR_INVALID_ARG, "route must be -1, 0, 1 or 2");
+  g_sort_rows_route.store(route);
+  return SRS_OK;
+}
+
+int srs_debug_last_sort_rows(int64_t* info) {
+  if (!info) return fail(SRS_ERR_INVALID_ARG, "info is NULL");
+  Workspace* W = nullptr;
+  WsLock lk;
+  SRS_TRY(acquire_ws(&W, &lk));
+  for (int i = 0; i < 4; i++) info[i] = W->sort_rows_info[i];
+  return SRS_OK;
+}
 
 }  // extern "C"

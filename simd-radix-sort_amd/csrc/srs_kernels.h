@@ -202,4 +202,22 @@ constexpr int kRowsWaveMax = 256;
 // kTopkRowsMaxK and row_len < 2^31, the row is read from memory once per pass.
 hipError_t launch_topk_rows(int key_size, TopkRowsArgs& a, bool stream, hipStream_t st);
 
+// ---- row-wise sort -----------------------------------------
+// The work list of `rows` dense rows of row_len records: row r becomes
+// Seg{r * row_len, row_len, rbits, buf} at list[r], and *ctr the counters of
+// that one list (cls 0: the small local class, 1: the large one, 2: the big
+// list). list holds at least `rows` entries.
+hipError_t launch_rows_segs(Seg* list, int64_t rows, int64_t row_len, int rbits, int buf, int cls,
+                            ListCounters* ctr, hipStream_t st);
+// Strided rows made dense: record i of row r of column c moves from
+// col[c].in + (r * row_stride + i) * width to col[c].out + (r * row_len + i) *
+// width; idx_out (or null) receives i at r * row_len + i.
+struct RowsPrepareArgs {
+  int64_t rows, row_len, row_stride;
+  int32_t ncols;
+  int64_t* idx_out;
+  TopkRowsCol col[SRS_MAX_COLS];
+};
+hipError_t launch_rows_prepare(const RowsPrepareArgs& a, hipStream_t st);
+
 }  // namespace srs

@@ -5562,4 +5562,88 @@ hipError_t launch_topk_rows(int key_size, TopkRowsArgs& a, bool stream, hipStrea
   return err != hipSuccess ? err : hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// row-wise sort (srs_sort_rows_soa_device): the front end of
+// the segment machinery for the rows of a matrix. Plain kernels in stream
+// order: no workgroup reads what another wrote in the same launch.
+// ---------------------------------------------------------------------------
+constexpr int kRowsSegsThreads = 256;
+constexpr int kRowsPrepThreads = 256;
+constexpr int kRowsPrepItems = 4;
+
+// One thread per row: row r is segment r of its list (every position is
+// known, so nothing is counted); thread 0 of the grid writes the counters.
+// Rows of one length land in one list: `list` is the small class's, the large
+// class's or the big list, as len decides (cls: 0 / 1 / 2).
+__global__ __launch_bounds__(kRowsSegsThreads) void rows_segs_kernel(
+    Seg* __restrict__ list, int64_t rows, int64_t row_len, int32_t rbits, int32_t buf, int cls,
+    ListCounters* __restrict__ ctr) {
+  const int64_t r = (int64_t)blockIdx.x * kRowsSegsThreads + threadIdx.x;
+  if (r == 0) {
+    ListCounters c{};
+    const unsigned long long m = (unsigned long long)rows;
+    if (cls == 0) c.n_local = m;
+    else if (cls == 1) c.n_local2 = m;
+    else c.n_big = m;
+    c.local_elems = cls < 2 ? m * (unsigned long long)row_len : 0;
+    *ctr = c;
+  }
+  if (r >= rows) return;
+  list[r] = Seg{r * row_len, row_len, rbits, buf};
+}
+
+// Strided rows -> dense rows, one pass over every column, and the iota of the
+// in-row positions into the index column. Thread t of a block takes records
+// t, t + 256, ... of the block's 1024 consecutive dense positions, so a wave
+// reads and writes 64 neighbouring elements of each column (a row boundary
+// inside the strip breaks the read into two runs).
+__global__ __launch_bounds__(kRowsPrepThreads) void rows_prepare_kernel(const RowsPrepareArgs A) {
+  const int64_t total = A.rows * A.row_len;
+  const int64_t e0 = (int64_t)blockIdx.x * (kRowsPrepThreads * kRowsPrepItems) + threadIdx.x;
+  int64_t src[kRowsPrepItems], pos[kRowsPrepItems];
+#pragma unroll
+  for (int k = 0; k < kRowsPrepItems; k++) {
+    const int64_t e = e0 + k * kRowsPrepThreads;
+    const int64_t r = e < total ? e / A.row_len : 0;
+    pos[k] = e - r * A.row_len;
+    src[k] = r * A.row_stride + pos[k];
+  }
+  for (int c = 0; c < A.ncols; c++) {
+    const TopkRowsCol C = A.col[c];
+    with_width(C.width, [&](auto W_) {
+      constexpr int W = decltype(W_)::value;
+      uint64_t v[kRowsPrepItems] = {};
+#pragma unroll
+      for (int k = 0; k < kRowsPrepItems; k++)
+        if (e0 + k * kRowsPrepThreads < total) v[k] = ldw<W>(C.in + src[k] * W);
+#pragma unroll
+      for (int k = 0; k < kRowsPrepItems; k++)
+        if (e0 + k * kRowsPrepThreads < total) stw<W>(C.out + (e0 + k * kRowsPrepThreads) * W, v[k]);
+    });
+  }
+  if (A.idx_out) {
+#pragma unroll
+    for (int k = 0; k < kRowsPrepItems; k++)
+      if (e0 + k * kRowsPrepThreads < total)
+        gst<int64_t>(A.idx_out + e0 + k * kRowsPrepThreads, pos[k]);
+  }
+}
+
+hipError_t launch_rows_segs(Seg* list, int64_t rows, int64_t row_len, int rbits, int buf, int cls,
+                            ListCounters* ctr, hipStream_t st) {
+  const int64_t grid = (rows + kRowsSegsThreads - 1) / kRowsSegsThreads;
+  if (rows <= 0 || grid > 0x7fffffff) return hipErrorInvalidValue;
+  rows_segs_kernel<<<(unsigned)grid, kRowsSegsThreads, 0, st>>>(list, rows, row_len, rbits, buf,
+                                                                cls, ctr);
+  return hipGetLastError();
+}
+
+hipError_t launch_rows_prepare(const RowsPrepareArgs& a, hipStream_t st) {
+  constexpr int64_t per = kRowsPrepThreads * kRowsPrepItems;
+  const int64_t grid = (a.rows * a.row_len + per - 1) / per;
+  if (grid <= 0 || grid > 0x7fffffff) return hipErrorInvalidValue;
+  rows_prepare_kernel<<<(unsigned)grid, kRowsPrepThreads, 0, st>>>(a);
+  return hipGetLastError();
+}
+
 }  // namespace srs

@@ -83,6 +83,10 @@ def lib() -> ctypes.CDLL:
     L.srs_topk_rows_max_k.restype = i64
     L.srs_debug_set_topk_rows_route.argtypes = [ctypes.c_int]
     L.srs_debug_last_topk_rows.argtypes = [ctypes.POINTER(i64)]
+    L.srs_sort_rows_soa_device.argtypes = [i64, i64, i64, ctypes.c_int, ctypes.c_int, vp, i32, vp,
+                                           vp, vp, vp, vp, vp]
+    L.srs_debug_set_sort_rows_route.argtypes = [ctypes.c_int]
+    L.srs_debug_last_sort_rows.argtypes = [ctypes.POINTER(i64)]
     L.srs_fill_synthetic_device.argtypes = [i64, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
                                             vp, i32, vp, vp, vp]
     L.srs_key_histogram_device.argtypes = [i64, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp,
@@ -391,6 +395,59 @@ def topk_rows_device(keys, *payloads, k: int, up: bool = True, key_kind: int | N
     return out + ((idx,) if indices else ())
 
 
+SORT_ROWS_KERNEL, SORT_ROWS_LOCAL, SORT_ROWS_LEVELS = 0, 1, 2
+
+
+def sort_rows_device(keys, *payloads, up: bool = True, key_kind: int | None = None,
+                     indices: bool = False, out=None, stream=None):
+    """Every row of a matrix sorted in one call, out of place
+    (srs_sort_rows_soa_device): per row the stable sort by key, equal keys in
+    input order. The inputs are 2-D device tensors of equal shape (rows,
+    row_len) with stride(1) == 1 and equal stride(0) >= row_len (a sliced view
+    m[:, :L] works without a copy); they are not written. Returns (keys_out,
+    *payloads_out[, indices]) of shape (rows, row_len): `out` = (keys_out,
+    *payloads_out), contiguous and clear of the inputs, or new tensors;
+    indices=True adds an int64 tensor of each record's position inside its
+    row."""
+    import torch
+    cols = (keys,) + payloads
+    if keys.dim() != 2:
+        raise ValueError("keys must be a 2-D tensor (rows, row_len)")
+    rows, n = keys.shape
+    # (a matrix of one row or of one column may report any stride for that dim)
+    stride = keys.stride(0) if rows > 1 else max(n, 1)
+    for t in cols:
+        if not (t.is_cuda and t.dim() == 2 and tuple(t.shape) == (rows, n)):
+            raise ValueError("columns must be 2-D device tensors of equal shape")
+        if t.device != keys.device:
+            raise ValueError(f"columns must all be on {keys.device} (got {t.device})")
+        if (n > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) != stride) or stride < n:
+            raise ValueError("columns must have stride(1) == 1 and equal stride(0) >= row_len")
+    kind = _torch_kind(keys) if key_kind is None else int(key_kind)
+    if out is None:
+        out = tuple(torch.empty((rows, n), dtype=c.dtype, device=keys.device) for c in cols)
+    else:
+        out = tuple(out)
+        if len(out) != len(cols):
+            raise ValueError("out must hold keys_out followed by every payload_out")
+        for o, i in zip(out, cols):
+            if not (o.is_cuda and o.device == keys.device and o.is_contiguous() and
+                    o.numel() >= rows * n and o.element_size() == i.element_size()):
+                raise ValueError("out tensors must be contiguous, on the keys' GPU, of at least "
+                                 "rows * row_len elements and of their input's element size")
+    idx = torch.empty((rows, n), dtype=torch.int64, device=keys.device) if indices else None
+    if rows == 0 or n == 0:  # (an empty tensor has no address to pass)
+        return out + ((idx,) if indices else ())
+    with _on_device(keys):
+        _check(lib().srs_sort_rows_soa_device(
+            rows, n, stride, kind, int(bool(up)), keys.data_ptr(), len(payloads),
+            _ptr_array([p.data_ptr() for p in payloads]),
+            _size_array([p.element_size() for p in payloads]), out[0].data_ptr(),
+            _ptr_array([o.data_ptr() for o in out[1:]]),
+            None if idx is None else idx.data_ptr(), _stream_ptr(stream, keys.device)))
+    return out + ((idx,) if indices else ())
+
+
 def topk_combined_device(elements, key_kind: int, k: int, up: bool = True, out=None,
                          indices: bool = False, stream=None):
     """topk_device on a DataElement array (srs_topk_aos_device): `elements`
@@ -617,6 +674,21 @@ def debug_last_topk_rows():
     current device (synchronizes the device)."""
     c = (ctypes.c_int64 * 4)()
     _check(lib().srs_debug_last_topk_rows(c))
+    return tuple(int(x) for x in c)
+
+
+def debug_set_sort_rows_route(route: int) -> None:
+    """Route of sort_rows_device, process-wide (srs_debug_set_sort_rows_route):
+    -1 the library's rule, SORT_ROWS_KERNEL / _LOCAL / _LEVELS force one."""
+    _check(lib().srs_debug_set_sort_rows_route(int(route)))
+
+
+def debug_last_sort_rows():
+    """(route, kernel launches or -1 where they are not counted, host
+    read-backs, 1 if the prepare pass ran) of the last sort_rows_device on the
+    current device."""
+    c = (ctypes.c_int64 * 4)()
+    _check(lib().srs_debug_last_sort_rows(c))
     return tuple(int(x) for x in c)
 
 
