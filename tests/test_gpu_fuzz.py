@@ -6,10 +6,16 @@ in place or out of place): 600 seeded cases of random key kind, direction,
 size (log-uniform 1 .. 1.2M), key distribution and payload columns, each
 equal to a stable sort bit for bit (the GPU sort is stable; with n <=
 cmp_sort_threshold floats compare -0.0 == +0.0, as the reference's leaf).
+Cases 600 .. 679 are float keys of the "specials" distribution of
+tests/srs_fuzzlib.py: normals mixed with +-inf, +-0.0, denormals, the smallest
+normal and the largest finite value (the oracle's leaf, key_less in
+oracle/srs_oracle.c, compares IEEE values: +-inf and denormals by value, the
+two zeros equal, which is what stable_reference assumes).
 NaN keys are outside the contract and not generated."""
 import numpy as np
 import pytest
 
+from srs_fuzzlib import float_specials
 from srs_testlib import KIND_DTYPES, KIND_NAMES, KIND_UINT, stable_reference
 from test_gpu_sort import bytes_equal
 
@@ -18,6 +24,7 @@ pytestmark = pytest.mark.gpu
 srs_amd = pytest.importorskip("srs_amd")
 
 N_CASES = 600
+N_SPECIALS = 80  # cases N_CASES .. N_CASES + N_SPECIALS - 1: float keys, "specials"
 
 
 def _torch():
@@ -38,6 +45,8 @@ def _keys(kind, n, dist, rng):
             return (rng.integers(-50, 50, n) * 0.25).astype(dt)  # dups, +-0.0
         if dist == "const":
             return np.full(n, -0.0, dt)
+        if dist == "specials":
+            return float_specials(dt, n, rng)
         v = rng.uniform(-1, 1, n).astype(dt)
         v[rng.random(n) < 0.5] = 0.0
         return v
@@ -62,7 +71,7 @@ def _gpu():
     srs_amd.lib()
 
 
-@pytest.mark.parametrize("case", range(N_CASES))
+@pytest.mark.parametrize("case", range(N_CASES + N_SPECIALS))
 def test_fuzz_case(case):
     torch = _torch()
     rng = np.random.default_rng(1_000_003 * case + 17)
@@ -70,6 +79,8 @@ def test_fuzz_case(case):
     up = bool(rng.integers(0, 2))
     n = int(np.exp(rng.uniform(0, np.log(1_200_000))))
     dist = ["full", "narrow", "const", "skew"][int(rng.integers(0, 4))]
+    if case >= N_CASES:  # (the draws above stay those of every other case)
+        kind, dist = 8 + kind % 2, "specials"
     keys = _keys(kind, n, dist, rng)
     widths = [int(w) for w in rng.choice([1, 2, 4, 8], int(rng.integers(0, 3)))]
     pays = [rng.integers(0, 1 << (8 * w), n, dtype=np.uint64).astype(f"u{w}") for w in widths]
