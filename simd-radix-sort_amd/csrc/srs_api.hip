@@ -11,6 +11,20 @@
 //
 // Two small control read-backs per level (tile/histogram totals, list
 // counters) size the next launches. Everything else stays on the device.
+//
+// Sections, in order:
+//   errors and the environment knobs (every getenv of this file)
+//   kernel timing (TimedScope, the statistics bench.py reads by name)
+//   allocation: big_alloc, placed_alloc, ensure
+//   Workspace, WsScope (lock + stream order of one call)
+//   descriptors: Request, init_desc, set_columns
+//   one level: plan_balanced_level, plan_range_level (device halves; the
+//     arithmetic is srs_plan.hip), LevelSpec, run_level
+//   the sort: run_small, choose_layout, plan_first_level, start_lists,
+//     run_stripe_levels, run_sort, run_lists_tail, run_partition
+//   top-k, row-wise top-k, row-wise sort; validate_outputs
+//   host arrays: staging rings, host_sort_single, host_sort_split
+//   request builders and the C ABI
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -32,6 +46,7 @@
 #include "../../include/srs_c_api.h"
 #include "srs_common.h"
 #include "srs_kernels.h"
+#include "srs_plan.h"
 
 namespace srs {
 namespace {
@@ -44,35 +59,68 @@ unsigned long long* g_stamp_acc = nullptr;  // srs_debug_set_stamp_buffer
 uint32_t* g_lb_status = nullptr;             // srs_debug_set_lookback
 unsigned long long* g_lb_err = nullptr;
 
+// ---------------------------------------------------------------------------
+// environment knobs: the three parses, then every knob of the driver. The
+// ones with a `static` are read once per process, the others on every call
+// (tests set those inside a running process).
+// ---------------------------------------------------------------------------
+const char* knob_str(const char* name) { return getenv(name); }
+// a flag that is on unless the value starts with '0'
+bool knob_on(const char* name) {
+  const char* e = knob_str(name);
+  return !(e && *e == '0');
+}
+// a flag that is off unless the value is non-empty and does not start with '0'
+bool knob_set(const char* name) {
+  const char* e = knob_str(name);
+  return e && *e && *e != '0';
+}
+int64_t knob_int(const char* name, int64_t dflt) {
+  const char* e = knob_str(name);
+  return (e && *e) ? atoll(e) : dflt;
+}
+
+// read once per process:
+#define SRS_KNOB_ONCE(type, fn, expr) \
+  type fn() {                         \
+    static const type v = (expr);     \
+    return v;                         \
+  }
 // SRS_TRACE_LEVELS=1: one stderr line per global level and per local stage
 // (segment counts; diagnostics only, costs one extra read-back per sort)
-bool trace_levels() {
-  static const bool on = [] {
-    const char* e = getenv("SRS_TRACE_LEVELS");
-    return e && *e && *e != '0';
-  }();
-  return on;
-}
-
+SRS_KNOB_ONCE(bool, trace_levels, knob_set("SRS_TRACE_LEVELS"))
 // SRS_NO_DIRECT_LOCAL=1: the small local class always takes the fast kernel
-// (A/B runs of the direct kernel in one build)
-bool direct_local_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("SRS_NO_DIRECT_LOCAL");
-    return !(e && *e && *e != '0');
-  }();
-  return on;
+// (A/B runs of the direct kernel in one build); SRS_NO_DIRECT_LOCAL2=1: the
+// large class does
+SRS_KNOB_ONCE(bool, direct_local_enabled, !knob_set("SRS_NO_DIRECT_LOCAL"))
+SRS_KNOB_ONCE(bool, direct_local2_enabled, !knob_set("SRS_NO_DIRECT_LOCAL2"))
+// the stripe first level (SRS_NO_STRIPES=1: off)
+SRS_KNOB_ONCE(bool, stripes_enabled, !knob_set("SRS_NO_STRIPES"))
+// the home write through TMP2 (choose_layout; SRS_HOME_TMP2=0: off)
+SRS_KNOB_ONCE(bool, home_tmp2_enabled, knob_on("SRS_HOME_TMP2"))
+// the shard's plain-digit partition on the tile-pair scatter (SRS_PARTITION_PAIRS=0: off)
+SRS_KNOB_ONCE(bool, partition_pairs_enabled, knob_on("SRS_PARTITION_PAIRS"))
+// medium sorts: both local classes at once (run_lists_tail; SRS_LOCAL_FORK=0: off)
+SRS_KNOB_ONCE(bool, local_fork_enabled, knob_on("SRS_LOCAL_FORK"))
+// Mid-size sorts (kLocalCap < n <= kMidMaxKeys) take one launch with grid barriers
+// (launch_mid_sort, DESIGN.md §4); SRS_MID=0 sends them down the general path.
+SRS_KNOB_ONCE(bool, mid_enabled, knob_on("SRS_MID"))
+// the largest sort whose first level takes one launch (launch_mid_level);
+// SRS_MID_LEVEL_MAX (records, <= kMidLevelMaxKeys) for A/B runs, 0 off
+// (a float parse: "2e6")
+int64_t mid_level_max_knob() {
+  const char* e = knob_str("SRS_MID_LEVEL_MAX");
+  return std::min<int64_t>(e && *e ? (int64_t)atof(e) : kMidLevelMaxKeys, kMidLevelMaxKeys);
 }
-
-// the large-class direct kernel (SRS_NO_DIRECT_LOCAL2=1: the fast kernel
-// takes the large class, for A/B runs)
-bool direct_local2_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("SRS_NO_DIRECT_LOCAL2");
-    return !(e && *e && *e != '0');
-  }();
-  return on;
-}
+SRS_KNOB_ONCE(int64_t, mid_level_max_n, mid_level_max_knob())
+// read on every call: SRS_PLACE=0: plain allocations (A/B runs of placed_alloc)
+bool placement_enabled() { return knob_on("SRS_PLACE"); }
+// SRS_PAIR_TILES (A/B runs of the tile-pair scatter, pair_tiles_mode)
+int pair_tiles_knob() { return (int)knob_int("SRS_PAIR_TILES", 2); }
+// SRS_XCD_ROT (placement diagnostics)
+int xcd_rotation_knob() { return (int)knob_int("SRS_XCD_ROT", 0); }
+// SRS_TABLE (A/B runs: "1" or "3" forces the digit table's kind, plan_table)
+const char* table_knob() { return knob_str("SRS_TABLE"); }
 
 // Fewest small-class segments for which the direct kernel runs. Below it the
 // fast kernel alone is cheaper: the direct kernel's hand-over list costs one
@@ -82,10 +130,7 @@ bool direct_local2_enabled() {
 // with the direct kernel): 2^18 0.373 / 0.427, 2^22 0.068 / 0.079, 2^24
 // 0.0441 / 0.0447; at 1e9 (262144 segments) the direct kernel saves ~0.9 ms.
 // Read on every call (tests lower it to reach the kernel at small sizes).
-int64_t direct_min_segs() {
-  const char* e = getenv("SRS_DIRECT_MIN_SEGS");
-  return (e && *e) ? atoll(e) : 8192;
-}
+int64_t direct_min_segs() { return knob_int("SRS_DIRECT_MIN_SEGS", 8192); }
 
 int fail(int code, const std::string& msg) {
   g_err = msg;
@@ -241,7 +286,7 @@ std::mutex g_vmu;
 std::map<void*, VmmRec> g_vmm;
 
 int ws_alloc_mode() {
-  const char* e = getenv("SRS_WS_ALLOC");
+  const char* e = knob_str("SRS_WS_ALLOC");
   if (!e || !*e || !strcmp(e, "malloc")) return ALLOC_MALLOC;
   if (!strcmp(e, "contig")) return ALLOC_CONTIG;
   if (!strcmp(e, "vmm")) return ALLOC_VMM;
@@ -370,11 +415,6 @@ std::mutex g_plmu_map;                       // the map below
 std::map<int, std::unique_ptr<std::mutex>> g_plmu;
 std::mutex g_place_ref_mu;
 double g_place_ref = 0;  // fastest probe seen, ms per GB (0: none yet)
-
-bool placement_enabled() {
-  const char* e = getenv("SRS_PLACE");  // SRS_PLACE=0: plain allocations (A/B runs)
-  return !(e && *e == '0');
-}
 
 std::mutex& device_place_mutex(int dev) {
   std::lock_guard<std::mutex> g(g_plmu_map);
@@ -662,6 +702,18 @@ int acquire_ws(Workspace** out, WsLock* lk) {
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Where ncols columns of n elements sit in one buffer, each aligned to 256
+// bytes; returns the buffer's size.
+size_t col_offsets(int64_t n, int ncols, const uint32_t* widths, std::vector<size_t>* off) {
+  size_t total = 0;
+  off->clear();
+  for (int c = 0; c < ncols; c++) {
+    off->push_back(total);
+    total += align_up((size_t)n * widths[c], 256);
+  }
+  return total;
+}
+
 // Holds the workspace for one call on stream `st` (under W->mu): waits on the
 // device for the previous call's work on the workspace (any stream), and
 // marks the end of this call's work when it goes out of scope, also on error.
@@ -680,6 +732,18 @@ struct WsUse {
   }
 };
 
+// One call's hold on the current device's workspace: the lock, then (begin)
+// its place in the workspace's stream order. `use` goes first on scope exit.
+struct WsScope {
+  Workspace* W = nullptr;
+  WsLock lk;
+  WsUse use;
+  int lock() { return acquire_ws(&W, &lk); }
+  int begin(hipStream_t st) {
+    if (!W) SRS_TRY(lock());
+    return use.begin(W, st);
+  }
+};
 
 // ---------------------------------------------------------------------------
 // the sort driver (device pointers)
@@ -736,422 +800,42 @@ void key_masks(int kind, int up, SortDesc& d) {
   d.key_bits = kb;
 }
 
+// A zeroed descriptor with the key transform of (kind, up).
+SortDesc init_desc(int kind, int up) {
+  SortDesc d;
+  memset(&d, 0, sizeof d);
+  key_masks(kind, up, d);
+  return d;
+}
+
 // ---- balanced first level ---------------------------------------------------
 // A plain first digit (the top bits) is fine for uniform keys but wastes a
 // level on skewed ones: uniform floats in [-1, 1) put a quarter of all keys
 // under one exponent, so three levels are needed instead of two. For large
 // inputs a sampled 16-bit histogram (a few million keys in contiguous chunks)
-// decides; if some top-9-bit bucket would hold more than kSkew times its
-// share, the first level instead sends the keys to 512 key-range groups of
-// ~equal size through a 16-bit digit table (the multi-GPU partition's LUT
-// digit). Each group's children start below the key prefix its bins share.
+// decides; if some top-9-bit bucket would hold more than kBalancedSkew times
+// its share, the first level instead sends the keys to 512 key-range groups of
+// ~equal size through a digit table (plan_table, srs_plan.hip).
 constexpr int64_t kBalancedMinN = int64_t(1) << 24;
 constexpr int kBalancedSkew = 4;
-constexpr int kGroups = kMaxBins;
 
-// *spread (also without a table): the sample's top 9 bits spread the keys
-// (no bucket above kBalancedSkew times its share), so a plain first digit
-// partitions them well.
-// The digit table of a balanced first level, planned from the sampled
-// 16-bit histogram h of the transformed keys (n input keys): mode 0 (no
-// table: it would not beat the plain digit), 1 (16-bit bins -> groups,
-// lut16) or 3 (split table, tab3), each group's rbits, and the predicted
-// keys the next level leaves above the LDS capacity (over; over_other for
-// the table not taken). Host only; srs_debug_plan_table exposes it.
-struct TablePlan {
-  int mode = 0;
-  std::vector<int32_t> lut16, tab3, rbits;
-  int groups = 0;
-  double over = 0, over_other = 0;
+// What the key sample decided about the first level (plan_first_level).
+struct FirstLevel {
+  bool balanced = false;      // a digit-table or range level runs first
+  // the sample's top 9 bits spread the keys (no bucket above kBalancedSkew
+  // times its share), so a plain first digit partitions them well
+  bool spread = false;
+  bool ranges = false;        // that level is a range level (plan_range_level)
+  bool ranges_final = false;  // and each of its buckets holds one key value
+  bool one_value = false;     // all keys are equal: nothing to sort
+  int lut_entries = 0, lut_mode = 1;  // the digit table's (SortDesc)
 };
 
-void plan_table(const std::vector<uint32_t>& h, int64_t n, int key_bits, TablePlan* P) {
-  *P = TablePlan();
-
-
-  // (host time here is GPU idle time: every pass below looks only at the
-  // non-empty bins or is a plain integer sweep)
-  std::vector<uint64_t> ct(512, 0);
-  std::vector<int32_t> nz;  // the non-empty bins
-  nz.reserve(8192);
-  for (int b0 = 0; b0 < 65536; b0 += 16) {  // (skips empty runs 16 bins at a time)
-    uint64_t any = 0;
-    for (int j = 0; j < 16; j++) any |= h[b0 + j];
-    if (!any) continue;
-    for (int b = b0; b < b0 + 16; b++)
-      if (h[b]) {
-        nz.push_back(b);
-        ct[b >> 7] += h[b];
-      }
-  }
-  uint64_t total = 0;
-  for (uint64_t c : ct) total += c;
-  if (total == 0) return;
-  // Bins -> groups. Candidate groupings of the 16-bit bins into 512 key-range
-  // groups; the one whose next level is predicted to leave the fewest keys in
-  // buckets above the LDS capacity wins (a group's next digit splits its key
-  // range evenly, so a group that mixes bins of different key density, e.g.
-  // two float exponents, overfills the buckets of the denser one: C2 had 2101
-  // such buckets, 5 % of its keys, taking a third and fourth level):
-  //  * cumulative: group of bin b = floor(G * (keys before b + half of b) / total);
-  //  * bin-aligned: a top-9-bit bin worth at least one group gets groups of its
-  //    own, cut at 16-bit bins by key counts; bins worth less share groups of
-  //    at most one share.
-  const double to_n = (double)n / (double)total;  // sample -> input keys
-  // predicted keys the next level leaves in buckets above kLocalCap (keys
-  // uniform inside a 16-bit bin), or that need two more levels
-  std::vector<double> qsum(kMaxBins, 0.0);
-  auto overflow = [&](const std::vector<int32_t>& L) -> double {
-    // a group's bins are one run of the (monotone) table
-    std::vector<int32_t> fst(kGroups, -1), lst(kGroups, -1), nz0(kGroups, 0), nz1(kGroups, 0);
-    std::vector<uint64_t> cnt(kGroups, 0);
-    // each group's run of the (monotone) table: one forward sweep that
-    // gallops over each run instead of stepping through 65,536 entries
-    for (int b = 0; b < 65536;) {
-      const int g = L[b];
-      int step = 1;
-      while (b + step < 65536 && L[b + step] == g) step <<= 1;
-      int lo = b + (step >> 1), hi = std::min(b + step, 65536);  // last g in [lo, hi)
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (L[mid] == g) lo = mid;
-        else hi = mid;
-      }
-      fst[g] = b;
-      lst[g] = lo;
-      b = lo + 1;
-    }
-    for (size_t i = 0; i < nz.size(); i++) {  // the group's non-empty bins: nz[nz0, nz1)
-      const int g = L[nz[i]];
-      if (!cnt[g]) nz0[g] = (int32_t)i;
-      nz1[g] = (int32_t)i + 1;
-      cnt[g] += h[nz[i]];
-    }
-    double over = 0;
-    for (int g = 0; g < kGroups; g++) {
-      const double len = (double)cnt[g] * to_n;
-      if (len <= kLocalCap) continue;
-      int bl = 0;
-      while ((1 << bl) <= (fst[g] ^ lst[g])) bl++;
-      int need;
-      if (levels_for((int64_t)len, kLocalCapTarget, &need) > 1) {
-        over += len;
-        continue;
-      }
-      const int bits = choose_bits((int64_t)len, key_bits - (16 - bl));
-      if (bits >= bl) {  // each bin splits into 2^(bits - bl) buckets
-        const double lim = (double)kLocalCap * (double)(1 << (bits - bl)) / to_n;
-        const double lim3 = lim + 3.0 * std::sqrt(lim);  // (sample noise)
-        for (int i = nz0[g]; i < nz1[g]; i++)
-          if ((double)h[nz[i]] > lim3) over += h[nz[i]] * to_n;
-      } else {  // each bucket spans 2^(bl - bits) bins of the aligned range
-        const int sh = bl - bits, b0 = fst[g] & ~((1 << bl) - 1);
-        int qlo = kMaxBins, qhi = -1;
-        for (int i = nz0[g]; i < nz1[g]; i++) {
-          const int q = (nz[i] - b0) >> sh;
-          qsum[q] += h[nz[i]];
-          qlo = std::min(qlo, q);
-          qhi = std::max(qhi, q);
-        }
-        const double lim = (double)kLocalCap / to_n, lim3 = lim + 3.0 * std::sqrt(lim);
-        for (int q = qlo; q <= qhi; q++) {
-          if (qsum[q] > lim3) over += qsum[q] * to_n;
-          qsum[q] = 0;
-        }
-      }
-    }
-    return over;
-  };
-  // The 16-bit-table candidates (DigitLut mode 1, below) are planned only
-  // when the split table's predicted overflow is not already zero (they cost
-  // ~0.3 ms of host time, during which the GPU waits).
-  std::vector<int32_t> lut(65536), first(kGroups, -1), last(kGroups, -1), rbits(kGroups);
-  double over_best = -1;  // (-1: not evaluated)
-  int buckets_used = 0, groups_used = 0;
-  for (int t = 0; t < 512; t++) buckets_used += ct[t] != 0;
-  // false: no table pays
-  auto plan_mode1 = [&]() -> bool {
-    {  // (an empty bin takes the group before it)
-      double before = 0;
-      int g = 0, at = 0;
-      for (int b : nz) {
-        std::fill(lut.begin() + at, lut.begin() + b, g);
-        const int x = (int)((before + 0.5 * h[b]) * kGroups / (double)total);
-        g = std::min(std::max(x, g), kGroups - 1);
-        lut[b] = g;
-        at = b + 1;
-        before += h[b];
-      }
-      std::fill(lut.begin() + at, lut.end(), g);
-    }
-    over_best = overflow(lut);
-    {
-      std::vector<int32_t> la(65536, 0);
-      std::vector<double> x(512);
-      for (int t = 0; t < 512; t++) x[t] = (double)kGroups * (double)ct[t] / (double)total;
-      for (double sc = 1.0; sc > 0.5; sc -= 0.005) {
-        std::vector<int> nt(512, 0);
-        int S = 0;
-        double acc = 0;
-        bool open = false;
-        for (int t = 0; t < 512; t++) {
-          if (!ct[t]) continue;
-          if (x[t] < 1.0) {
-            if (!open || acc + x[t] > 1.0) {
-              S++;
-              open = true;
-              acc = 0;
-            }
-            acc += x[t];
-            continue;
-          }
-          open = false;
-          nt[t] = std::min(128, std::max(1, (int)std::lround(x[t] * sc)));
-          S += nt[t];
-        }
-        if (S > kGroups) continue;
-        int g = -1;
-        acc = 0;
-        open = false;
-        for (int t = 0; t < 512; t++) {
-          if (!ct[t] || x[t] < 1.0) {
-            if (ct[t] && (!open || acc + x[t] > 1.0)) {
-              g++;
-              open = true;
-              acc = 0;
-            }
-            acc += x[t];
-            for (int j = 0; j < 128; j++) la[t * 128 + j] = std::max(g, 0);
-            continue;
-          }
-          open = false;
-          const int base = g + 1;
-          double before = 0;
-          int prev = 0;
-          for (int j = 0; j < 128; j++) {
-            const double hj = h[t * 128 + j];
-            int k = (int)((before + 0.5 * hj) * nt[t] / (double)ct[t]);
-            k = std::min(std::max(k, prev), nt[t] - 1);
-            prev = k;
-            la[t * 128 + j] = base + k;
-            before += hj;
-          }
-          g = base + nt[t] - 1;
-        }
-        const double o = overflow(la);
-        if (o <= over_best) {
-          over_best = o;
-          lut.swap(la);
-        }
-        break;
-      }
-    }
-    for (int b = 0; b < 65536; b++) {
-      const int g = lut[b];
-      if (first[g] < 0) first[g] = b;
-      last[g] = b;
-    }
-    // the table only pays when its groups outnumber the plain digit's
-    // non-empty buckets (Gaussian int64 keys fill two 16-bit bins: both ways
-    // give two buckets, and the table pass is the slower one)
-    {
-      std::vector<uint8_t> has(kGroups, 0);
-      for (int b : nz) has[lut[b]] = 1;
-      for (int g = 0; g < kGroups; g++) groups_used += has[g];
-    }
-    if (groups_used < 2 * buckets_used) return false;
-    for (int g = 0; g < kGroups; g++) {
-      const int diff = first[g] < 0 ? 0xFFFF : (first[g] ^ last[g]);
-      int bl = 0;
-      while ((1 << bl) <= diff) bl++;
-      rbits[g] = key_bits - (16 - bl);  // the group's keys share 16 - bl top bits
-    }
-    return true;
-  };
-  // Split table (DigitLut mode 3), when its next level overflows no more:
-  // each top-9-bit bin t gets 2^lg_t consecutive groups, the next lg_t key
-  // bits (no group spans two bins unless both are worth less than a group).
-  // One 2 KB table and one lookup per key instead of the two-level 16-bit
-  // table (up to 24 KB staged per tile, two dependent lookups).
-  {
-    const int kb = key_bits;
-    // A group's rbits bounds every key code the table sends it, so a group
-    // that takes a run of empty bins, or bins of different key density (two
-    // float exponents), gets a next digit that splits the keys it holds
-    // badly: C2's first group took the 128 empty bins below -1.0 (rbits 31)
-    // and left 1.95 M keys in one bucket, its shared tail group put one
-    // exponent's keys into a sixteenth of its buckets. When they fit, every
-    // non-empty bin gets groups of its own and every run of empty bins one
-    // group (which stays empty unless the sample missed keys). Otherwise bins
-    // worth less than one group share groups (consecutive, at most one share
-    // each) and empty bins join the group before them.
-    std::vector<int> lg(512, -1);     // own groups 2^lg; -1: none
-    std::vector<int> share(512, -1);  // >= 0: index of the shared group it joins
-    int S = 0;
-    int nonempty = 0, empty_runs = 0;
-    for (int t = 0; t < 512; t++) {
-      nonempty += ct[t] != 0;
-      empty_runs += !ct[t] && (t == 0 || ct[t - 1]);
-    }
-    const bool own = nonempty + empty_runs <= 512;
-    if (own) {
-      S = empty_runs;
-      for (int t = 0; t < 512; t++) {
-        if (!ct[t]) continue;
-        const double x = 512.0 * (double)ct[t] / (double)total;
-        int l = 0;
-        while (l < 9 && (double)(2 << l) <= x * 1.4142) l++;  // (nearest power of two)
-        lg[t] = l;
-        S += 1 << l;
-      }
-    } else {
-      double acc = 0;
-      int nsh = 0;
-      bool open = false;
-      for (int t = 0; t < 512; t++) {
-        if (!ct[t]) continue;
-        const double x = 512.0 * (double)ct[t] / (double)total;
-        if (x < 1.0) {
-          if (!open || acc + x > 1.0) {
-            nsh++;
-            S++;
-            open = true;
-            acc = 0;
-          }
-          share[t] = nsh - 1;
-          acc += x;
-          continue;
-        }
-        open = false;
-        int l = 0;
-        while (l < 9 && (double)(2 << l) <= x * 1.4142) l++;  // (nearest power of two)
-        lg[t] = l;
-        S += 1 << l;
-      }
-    }
-    auto gsize = [&](int t, int l) { return (double)ct[t] / (double)(1 << l); };
-    {  // over budget: halve where the resulting groups stay smallest (min-heap)
-      std::priority_queue<std::pair<double, int>, std::vector<std::pair<double, int>>,
-                          std::greater<std::pair<double, int>>> q;
-      for (int t = 0; t < 512; t++)
-        if (lg[t] > 0) q.push({gsize(t, lg[t] - 1), t});
-      while (S > 512 && !q.empty()) {
-        const int t = q.top().second;
-        q.pop();
-        S -= 1 << (lg[t] - 1);
-        lg[t]--;
-        if (lg[t] > 0) q.push({gsize(t, lg[t] - 1), t});
-      }
-    }
-    {  // spare budget: split the largest groups that still fit (max-heap; a
-       // bin whose doubling does not fit now never will: the budget only shrinks)
-      std::priority_queue<std::pair<double, int>> q;
-      for (int t = 0; t < 512; t++)
-        if (lg[t] >= 0 && lg[t] < 9) q.push({gsize(t, lg[t]), t});
-      while (!q.empty()) {
-        const int t = q.top().second;
-        q.pop();
-        if (S + (1 << lg[t]) > 512) continue;
-        S += 1 << lg[t];
-        lg[t]++;
-        if (lg[t] < 9) q.push({gsize(t, lg[t]), t});
-      }
-    }
-    // the same grouping at 16-bit resolution (representable while lg <= 7)
-    bool repr = S <= 512;
-    std::vector<int32_t> l3(65536, 0);
-    {
-      int run = 0, cur_share = -1;
-      for (int t = 0; t < 512 && repr; t++) {
-        if (lg[t] < 0) {
-          int g;
-          if (own) {  // (an empty bin: its run's group)
-            g = (t == 0 || ct[t - 1]) ? run++ : run - 1;
-          } else if (share[t] >= 0 && share[t] != cur_share) {
-            cur_share = share[t];
-            g = run++;
-          } else {
-            g = run > 0 ? run - 1 : 0;
-          }
-          for (int j = 0; j < 128; j++) l3[t * 128 + j] = g;
-          continue;
-        }
-        if (lg[t] > 7) {
-          repr = false;
-          break;
-        }
-        for (int j = 0; j < 128; j++) l3[t * 128 + j] = run + (j >> (7 - lg[t]));
-        run += 1 << lg[t];
-      }
-    }
-    const double over3 = repr ? overflow(l3) : 1e300;
-    const char* force = getenv("SRS_TABLE");  // (A/B runs: "1" or "3" forces the table kind)
-    const bool forced = force && *force;
-    const bool early = !forced && repr && over3 == 0 &&
-                       S - (own ? empty_runs : 0) >= 2 * buckets_used;
-    if (!early && !plan_mode1()) return;
-    const bool take3 = forced ? (*force == '3' && repr) : (early || (repr && over3 <= over_best));
-    if (take3) {
-      // entry t: first group (bits 0..15) | lg (16..23); shared and empty
-      // bins: the group (lg 0)
-      std::vector<int32_t> tab(512);
-      std::vector<uint64_t> glo(kGroups, ~0ull), ghi(kGroups, 0);
-      const int unit = kb - 9;  // key bits below the top 9
-      for (int t = 0; t < 512; t++) {
-        const uint64_t t0 = (uint64_t)t << unit;
-        const int l = lg[t] < 0 ? 0 : lg[t];
-        const int g0 = l3[t * 128];
-        tab[t] = g0 | (l << 16);
-        const int sub = unit - l;
-        for (int j = 0; j < (1 << l); j++) {
-          const uint64_t a0 = t0 + ((uint64_t)j << sub);
-          glo[g0 + j] = std::min(glo[g0 + j], a0);
-          ghi[g0 + j] = std::max(ghi[g0 + j], a0 + ((uint64_t(1) << sub) - 1));
-        }
-      }
-      for (int g = 0; g < kGroups; g++) {
-        if (glo[g] > ghi[g]) {
-          rbits[g] = kb;  // (no keys)
-          continue;
-        }
-        const uint64_t x = glo[g] ^ ghi[g];
-        rbits[g] = x ? 64 - __builtin_clzll(x) : 0;
-      }
-      P->mode = 3;
-      P->tab3 = tab;
-      P->rbits = rbits;
-      P->groups = S;
-      P->over = over3;
-      P->over_other = over_best;
-      return;
-    }
-    P->over_other = over3;
-  }
-  P->mode = 1;
-  P->lut16 = lut;
-  P->rbits = rbits;
-  P->groups = groups_used;
-  P->over = over_best;
-}
-
-// *clusters (SoA only): the sampled keys form at most kMaxRanges clusters of
-// at most kClusterSpan adjacent 16-bit bins each (e.g. the reference's
-// Gaussian keys: one cluster around 0 for signed keys, two at both ends of
-// the range for unsigned ones): a range level decides (plan_range_level), no
-// digit table. Empty otherwise.
-struct KeyCluster {
-  int b0, b1;    // first and last sampled 16-bit bin
-  uint64_t cnt;  // sampled keys
-};
-constexpr int kClusterGap = 4096;  // bins between two clusters
-constexpr int kClusterSpan = 256;  // bins a cluster may cover
-
-int plan_balanced_level(Workspace* W, const Request& R, const SortDesc& d, bool* use,
-                        int* lut_entries, int* lut_mode, hipStream_t st, bool* spread,
-                        std::vector<KeyCluster>* clusters) {
-  *use = false;
-  *lut_mode = 1;
-  *spread = false;
+// The sample and what follows from it on the host: F->spread, the key
+// clusters (then a range level decides), or the digit table (F->balanced,
+// uploaded to W->lut / W->lut_rbits).
+int plan_balanced_level(Workspace* W, const Request& R, const SortDesc& d, hipStream_t st,
+                        FirstLevel* F, std::vector<KeyCluster>* clusters) {
   clusters->clear();
   const int ks = key_size_of(R.kind);
   const int64_t n = R.num;
@@ -1179,44 +863,33 @@ int plan_balanced_level(Workspace* W, const Request& R, const SortDesc& d, bool*
   // (not with canon_zero: the range level's exact min / max are taken over
   // the raw transformed keys, while its passes map -0.0 onto +0.0's code,
   // which can lie outside them)
-  if (!R.aos && !d.canon_zero) {
-    std::vector<KeyCluster> cl;
-    bool ok = true;
-    for (int b = 0; b < 65536 && ok; b++) {  // (stops at the first cluster too many or too wide)
-      if (!h[b]) continue;
-      if (cl.empty() || b - cl.back().b1 > kClusterGap) cl.push_back(KeyCluster{b, b, 0});
-      cl.back().b1 = b;
-      cl.back().cnt += h[b];
-      ok = (int)cl.size() <= kMaxRanges && cl.back().b1 - cl.back().b0 < kClusterSpan;
-    }
-    if (ok) {
-      *clusters = cl;
-      return SRS_OK;
-    }
-  }
+  if (!R.aos && !d.canon_zero && find_clusters(h, clusters)) return SRS_OK;
   if (top9max * 512 <= (uint64_t)kBalancedSkew * total) {
-    *spread = true;
+    F->spread = true;
     return SRS_OK;
   }
   if (R.aos) return SRS_OK;  // (the digit table is not used for AoS records)
   TablePlan P;
-  plan_table(h, n, d.key_bits, &P);
+  plan_table(h, n, d.key_bits, table_knob(), &P);
   if (trace_levels() && P.mode)
     fprintf(stderr, "[srs] digit table mode %d: %d groups, predicted overflow %.0f keys (other "
             "table %.0f)\n", P.mode, P.groups, P.over, P.over_other);
   if (P.mode == 0) return SRS_OK;
-  std::vector<int32_t>& rbits = P.rbits;
-  if (P.mode == 3) {
-    SRS_TRY(ensure(W->lut, 512 * sizeof(int32_t)));
+  // the table (`bytes` of it, in a buffer of `room`) and the groups' rbits
+  auto upload = [&](const void* table, size_t bytes, size_t room) -> int {
+    SRS_TRY(ensure(W->lut, room));
     SRS_TRY(ensure(W->lut_rbits, kGroups * sizeof(int32_t)));
-    HIP_TRY(hipMemcpyAsync(W->lut.p, P.tab3.data(), 512 * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(W->lut_rbits.p, rbits.data(), rbits.size() * 4, hipMemcpyHostToDevice,
-                           st));
+    HIP_TRY(hipMemcpyAsync(W->lut.p, table, bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(W->lut_rbits.p, P.rbits.data(), P.rbits.size() * 4,
+                           hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));  // the host vectors go out of scope
-    *lut_entries = 1024;  // (u16 units)
-    *lut_mode = 3;
-    *use = true;
+    F->balanced = true;
     return SRS_OK;
+  };
+  if (P.mode == 3) {
+    F->lut_entries = 1024;  // (u16 units)
+    F->lut_mode = 3;
+    return upload(P.tab3.data(), 512 * 4, 512 * sizeof(int32_t));
   }
   const std::vector<int32_t>& lut = P.lut16;
   // two-level u16 table (DigitLut mode 1): a 12-bit bin whose 16 sub-bins
@@ -1234,15 +907,9 @@ int plan_balanced_level(Workspace* W, const Request& R, const SortDesc& d, bool*
     }
   }
   if ((int)t2.size() > kLdsLutEntries) return fail(SRS_ERR_INTERNAL, "digit table too large");
-  *lut_entries = (int)t2.size();
-  SRS_TRY(ensure(W->lut, align_up(t2.size() * sizeof(uint16_t), 16)));  // staged in 16-byte loads
-  SRS_TRY(ensure(W->lut_rbits, kGroups * sizeof(int32_t)));
-  HIP_TRY(hipMemcpyAsync(W->lut.p, t2.data(), t2.size() * 2, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(W->lut_rbits.p, rbits.data(), rbits.size() * 4, hipMemcpyHostToDevice,
-                         st));
-  HIP_TRY(hipStreamSynchronize(st));  // the host vectors go out of scope
-  *use = true;
-  return SRS_OK;
+  F->lut_entries = (int)t2.size();
+  // (staged in 16-byte loads)
+  return upload(t2.data(), t2.size() * 2, align_up(t2.size() * sizeof(uint16_t), 16));
 }
 
 // The tile-pair scatter (scatter_pair_kernel): where it
@@ -1258,8 +925,7 @@ int plan_balanced_level(Workspace* W, const Request& R, const SortDesc& d, bool*
 // SRS_PAIR_TILES (A/B runs): 0 off, 1 every plain-digit level, 3 every
 // supported level, 2 (or unset) the default.
 int pair_tiles_mode(const SortDesc& d, int ks, bool aos_slices) {
-  const char* e = getenv("SRS_PAIR_TILES");
-  const int mode = e && *e ? atoi(e) : 2;
+  const int mode = pair_tiles_knob();
   if (mode == 0 || d.canon_zero || (ks != 4 && ks != 8)) return 0;
   // (the kernel holds column 0 in a register of the key's width: an AoS
   // record wider than its key, e.g. DataElement<float, uint32>, is not for it)
@@ -1284,25 +950,37 @@ struct LevelState {
 // One global MSB level over every large segment in W->big[S.cur]:
 // plan -> bases -> count -> offsets + children -> scatter. Children go to
 // W->big[S.cur ^ 1] / the local lists / the copy list; S is updated from the
-// device counters. force_bits / lut: partition passes (srs_partition_device).
-// How a level reads and hands on its segments: mode 0 plain; 1 a stripe
-// level (its segments are stripes of the input, partitioned each on its own;
-// the next level's segments are the buckets, read through a gathered tile
-// table); 2 that gathered level. See GTile (srs_common.h).
-struct LevelMode {
-  int mode = 0;
-  const GTile* gt = nullptr;        // mode 2
-  const int32_t* nt_over = nullptr; // mode 2: tiles per segment
-  const int32_t* torder = nullptr;  // mode 2: the count's tile order (stripe-major)
-  int key_bits = 0;                 // mode 1
+// device counters. What the level is comes in as a LevelSpec; the default
+// one is a general level: every segment's digit chosen by the plan kernel.
+enum TableKind {
+  TABLE_NONE = 0,   // a plain digit
+  TABLE_ANY = 1,    // a digit table of any kind (SortDesc::digit_lut)
+  TABLE_SMALL = 2,  // a small kind (key ranges, split table: the kernels with the small LDS table)
+};
+// How a level reads and hands on its segments: 1 a stripe level (its
+// segments are stripes of the input, partitioned each on its own; the next
+// level's segments are the buckets, read through a gathered tile table); 2
+// that gathered level. See GTile (srs_common.h).
+enum StripeMode { STRIPE_NONE = 0, STRIPE_LEVEL = 1, STRIPE_GATHERED = 2 };
+struct LevelSpec {
+  int bits = 0;                     // the digit's width; 0: the plan kernel chooses per segment
+  bool plain = false;               // bits > 0: a plain digit of that width (else the table's)
+  TableKind table = TABLE_NONE;
+  const int32_t* rbits = nullptr;   // a table level: its groups' rbits (device)
+  StripeMode stripe = STRIPE_NONE;
+  const GTile* gt = nullptr;        // gathered level
+  const int32_t* nt_over = nullptr; // gathered level: tiles per segment
+  const int32_t* torder = nullptr;  // gathered level: the count's tile order (stripe-major)
+  int key_bits = 0;                 // stripe level
   bool home = false;                // every bucket of this level is final: scatter to OUT
 };
 
-// lut: 0 a plain digit, 1 a digit table of any kind, 2 a small kind (key
-// ranges, split table: the kernels with the small LDS table)
-int run_level(Workspace* W, int ks, const SortDesc* d_desc, LevelState& S, int force_bits,
-              int lut, hipStream_t st, const int32_t* lut_rbits = nullptr,
-              const LevelMode& M = LevelMode()) {
+int run_level(Workspace* W, int ks, const SortDesc* d_desc, LevelState& S, hipStream_t st,
+              const LevelSpec& M = LevelSpec()) {
+  // (the launchers' convention: a forced plain digit as a negative width)
+  const int force_bits = M.plain ? -M.bits : M.bits;
+  const int lut = (int)M.table;
+  const int32_t* lut_rbits = M.rbits;
   const int64_t nbig = S.nbig;
   ListCounters* d_ctr = (ListCounters*)W->ctr.p;
   uint64_t* d_totals = (uint64_t*)W->totals.p;
@@ -1392,7 +1070,7 @@ int run_level(Workspace* W, int ks, const SortDesc* d_desc, LevelState& S, int f
                    (uint32_t*)W->gsum.p, (uint64_t*)W->gofs.p, (uint64_t*)W->sbase.p,
                    offs32 ? nullptr : (uint64_t*)W->offs.p, offs32 ? (uint32_t*)W->offs.p : nullptr,
                    var, (Seg*)W->big[nxt].p, (Seg*)W->local.p,
-                   (Seg*)W->local2.p, (Seg*)W->copy.p, d_ctr, lut_rbits, st, M.mode,
+                   (Seg*)W->local2.p, (Seg*)W->copy.p, d_ctr, lut_rbits, st, (int)M.stripe,
                    (uint32_t*)W->prun.p);
   }
   if (g_lb_status)  // (diagnostic look-back: fresh status words per level)
@@ -1409,13 +1087,13 @@ int run_level(Workspace* W, int ks, const SortDesc* d_desc, LevelState& S, int f
                      offs32 ? (const uint32_t*)W->offs.p : nullptr, ntiles, lut, S.ncols, st,
                      M.gt);
   }
-  if (M.mode == 1) {
+  if (M.stripe == STRIPE_LEVEL) {
     // the buckets become the next level's segments (logical starts: where
     // they end up), their tiles the pieces every stripe holds of them
     // (a digit-table level consumes no fixed bits: its groups' prefixes
     // come from lut_rbits)
-    const int nb = 1 << std::abs(force_bits);
-    const int rbits = lut ? M.key_bits : M.key_bits - std::abs(force_bits);
+    const int nb = 1 << M.bits;
+    const int rbits = lut ? M.key_bits : M.key_bits - M.bits;
     launch_stripe_tables((const uint32_t*)W->prun.p, nbig, nb, (uint32_t*)W->ptile.p,
                          (uint64_t*)W->btot.p, (uint32_t*)W->bnt.p, rbits, BUF_TMP,
                          (Seg*)W->big[nxt].p, (int32_t*)W->nt_over.p, (uint32_t*)W->btile.p,
@@ -1526,9 +1204,7 @@ int run_small(Workspace* W, const Request& R, hipStream_t st) {
   const int ks = key_size_of(R.kind);
   const int64_t n = R.num;
   const bool inplace = is_inplace(R);
-  SortDesc d;
-  memset(&d, 0, sizeof d);
-  key_masks(R.kind, R.up, d);
+  SortDesc d = init_desc(R.kind, R.up);
   const bool is_float = R.kind == SRS_KEY_F32 || R.kind == SRS_KEY_F64;
   d.canon_zero = (is_float && n <= R.thresh) ? 1 : 0;
   d.leaf_skip = leaf_skip_of(R);
@@ -1594,14 +1270,6 @@ bool direct_layout_ok(const SortDesc& d, int pm, int ks) {
 
 constexpr int64_t kStripeMinN = int64_t(1) << 25;
 
-bool stripes_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("SRS_NO_STRIPES");
-    return !(e && *e && *e != '0');
-  }();
-  return on;
-}
-
 // Range level: the keys form a few narrow clusters (the
 // sample's KeyClusters). One exact pass finds each cluster's smallest and
 // largest key (split points halfway between the sampled clusters); the first
@@ -1611,19 +1279,15 @@ bool stripes_enabled() {
 // bucket's keys then share every bit above shift_c (its children's rbits):
 // Gaussian keys (~1200 values) take two levels and end single-valued in OUT,
 // instead of a level on the sign bit, count-only levels on shared bits and a
-// copy home. *final: every bucket holds one key value (shift 0 everywhere).
-// *one_value: all keys are equal.
+// copy home. The device half: the exact pass, the children's rbits, the
+// descriptor's range fields; the arithmetic is plan_ranges (srs_plan.hip).
+// F->ranges_final: every bucket holds one key value (shift 0 everywhere).
+// F->one_value: all keys are equal.
 int plan_range_level(Workspace* W, const Request& R, const std::vector<KeyCluster>& cl,
-                     SortDesc& d, hipStream_t st, bool* use, bool* final_lvl, bool* one_value) {
-  *use = *final_lvl = *one_value = false;
+                     SortDesc& d, hipStream_t st, FirstLevel* F) {
   const int ks = key_size_of(R.kind);
-  const int kb = 8 * ks;
-  const int K = (int)cl.size();
-  uint64_t hi[kMaxRanges] = {~0ull, ~0ull, ~0ull, ~0ull};
-  for (int k = 0; k + 1 < K; k++) {  // split halfway between the sampled clusters
-    const uint64_t mid_bin = ((uint64_t)cl[k].b1 + (uint64_t)cl[k + 1].b0 + 1) / 2;
-    hi[k] = (mid_bin << (kb - 16)) - 1;
-  }
+  uint64_t hi[kMaxRanges];
+  range_splits(cl, 8 * ks, hi);
   SRS_TRY(ensure(W->totals, 2 * kMaxRanges * sizeof(uint64_t)));
   unsigned long long* mm = (unsigned long long*)W->totals.p;
   uint64_t init[2 * kMaxRanges];
@@ -1636,42 +1300,14 @@ int plan_range_level(Workspace* W, const Request& R, const std::vector<KeyCluste
   launch_key_minmax(R.in_cols[0], ks, ks, R.num, d.mpos, d.mneg, hi, mm, st);
   HIP_TRY(hipMemcpyAsync(got.data(), mm, sizeof init, hipMemcpyDeviceToHost, st));
   SRS_TRY(sync_poll(st));
-  // the non-empty ranges (a range's keys: u in (hi[c-1], hi[c]])
-  struct Rg {
-    uint64_t mn, mx, cnt, hi;
-  };
-  std::vector<Rg> rg;
-  for (int c = 0; c < K; c++) {
-    if (got[2 * c] > got[2 * c + 1]) continue;  // no key fell into this range
-    rg.push_back(Rg{got[2 * c], got[2 * c + 1], std::max<uint64_t>(cl[c].cnt, 1), hi[c]});
-  }
-  if (rg.empty()) return SRS_OK;
-  if (rg.size() == 1 && rg[0].mn == rg[0].mx) {
-    *one_value = true;
-    return SRS_OK;
-  }
-  // one shift for every range: the smallest that fits all of them into the
-  // level's buckets (ranges keep their order: dense bucket bases)
-  const int R_ = (int)rg.size();
-  auto shr = [](uint64_t x, int s) { return s >= 64 ? 0 : x >> s; };
-  auto span = [&](int s) {
-    uint64_t t = 0;
-    for (const Rg& r : rg) t += shr(r.mx, s) - shr(r.mn, s) + 1;
-    return t;
-  };
-  int s = 0;
-  while (s < kb && span(s) > (uint64_t)kMaxBins) s++;
-  uint32_t used = 0;
+  RangePlan P;
+  plan_ranges(cl, hi, got.data(), 8 * ks, &P);
+  F->one_value = P.one_value;
+  if (!P.use) return SRS_OK;
+  const int s = P.shift;
   for (int c = 0; c < kMaxRanges; c++) {
-    d.rng_hi[c] = ~0ull;
-    d.rng_adj[c] = 0;
-  }
-  std::vector<int> base(R_);
-  for (int c = 0; c < R_; c++) {
-    d.rng_hi[c] = c + 1 < R_ ? rg[c].hi : ~0ull;
-    base[c] = (int)used;
-    d.rng_adj[c] = used - (uint32_t)shr(rg[c].mn, s);  // (wrapping)
-    used += (uint32_t)(shr(rg[c].mx, s) - shr(rg[c].mn, s) + 1);
+    d.rng_hi[c] = P.rng_hi[c];
+    d.rng_adj[c] = P.rng_adj[c];
   }
   // children's rbits: the bits above the shift are shared in a bucket
   std::vector<int32_t> rbits(kMaxBins, s);
@@ -1684,68 +1320,22 @@ int plan_range_level(Workspace* W, const Request& R, const std::vector<KeyCluste
   d.lut_bits = kMaxDigitBits;
   d.lut_shift = s;
   d.lut_entries = 0;
-  *use = true;
-  *final_lvl = s == 0;
+  F->ranges = true;
+  F->ranges_final = P.final_lvl;
   if (trace_levels())
-    for (int c = 0; c < R_; c++)
+    for (int c = 0; c < P.nranges; c++)
       fprintf(stderr, "[srs] range %d: keys [%llx, %llx] -> buckets from %d, shift %d\n", c,
-              (unsigned long long)rg[c].mn, (unsigned long long)rg[c].mx, base[c], s);
+              (unsigned long long)P.mn[c], (unsigned long long)P.mx[c], P.base[c], s);
   return SRS_OK;
 }
 
 int copy_through(const Request& R, hipStream_t st);
 
-// Mid-size sorts (kLocalCap < n <= kMidMaxKeys) take one launch with grid barriers
-// (launch_mid_sort, DESIGN.md §4); SRS_MID=0 sends them down the general path.
-// (below this a sort's columns stay in the L2 / Infinity Cache and the
-// placement of OUT does not matter)
+// the home write (choose_layout): below this a sort's columns stay in the
+// L2 / Infinity Cache and the placement of OUT does not matter
 constexpr int64_t kHomeTmp2MinN = int64_t(1) << 24;
-
-bool home_tmp2_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("SRS_HOME_TMP2");
-    return !(e && *e == '0');
-  }();
-  return on;
-}
-
-// the shard's plain-digit partition on the tile-pair scatter (SRS_PARTITION_PAIRS=0: off)
-bool partition_pairs_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("SRS_PARTITION_PAIRS");
-    return !(e && *e == '0');
-  }();
-  return on;
-}
-
-// medium sorts: both local classes at once (run_sort's local pass)
+// medium sorts: both local classes at once (run_lists_tail)
 constexpr int64_t kLocalForkMaxN = int64_t(1) << 24;
-bool local_fork_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("SRS_LOCAL_FORK");
-    return !(e && *e == '0');
-  }();
-  return on;
-}
-
-bool mid_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("SRS_MID");
-    return !(e && *e == '0');
-  }();
-  return on;
-}
-
-// the largest sort whose first level takes one launch (launch_mid_level);
-// SRS_MID_LEVEL_MAX (records, <= kMidLevelMaxKeys) for A/B runs, 0 off
-int64_t mid_level_max_n() {
-  static const int64_t v = [] {
-    const char* e = getenv("SRS_MID_LEVEL_MAX");
-    const int64_t x = e && *e ? (int64_t)atof(e) : kMidLevelMaxKeys;
-    return std::min<int64_t>(x, kMidLevelMaxKeys);
-  }();
-  return v;
-}
 
 // Waits for the mid-size kernel's MidFlag of call `seq`: a short poll, then
 // the stream (which also surfaces a kernel failure).
@@ -1767,43 +1357,57 @@ int run_lists_tail(Workspace* W, const Request& R, const SortDesc& d, const Sort
                    int64_t n_local, int64_t n_local2, int64_t n_copy, bool aos_cols,
                    hipStream_t st);
 
-int run_sort(Workspace* W, const Request& R, hipStream_t st) {
-  if (R.nsegs == 0 && R.num <= kLocalCap) return run_small(W, R, st);
-  {
-    const char* e = getenv("SRS_XCD_ROT");  // (placement diagnostics)
-    set_xcd_rotation(e && *e ? atoi(e) : 0);
-  }
-  W->last_small = false;
-  const int ks = key_size_of(R.kind);
-  const int64_t n = R.num;
-  const bool inplace = is_inplace(R);
+// The work lists, their counters and the level totals: room for n_big /
+// n_local / n_local2 entries to start with, 1024 at least (run_level grows
+// them for its children).
+int ensure_lists(Workspace* W, size_t n_big, size_t n_local, size_t n_local2) {
+  const size_t least = 1024;
+  SRS_TRY(ensure(W->big[0], std::max(least, n_big) * sizeof(Seg)));
+  SRS_TRY(ensure(W->big[1], least * sizeof(Seg)));
+  SRS_TRY(ensure(W->local, std::max(least, n_local) * sizeof(Seg)));
+  SRS_TRY(ensure(W->local2, std::max(least, n_local2) * sizeof(Seg)));
+  SRS_TRY(ensure(W->copy, least * sizeof(Seg)));
+  SRS_TRY(ensure(W->ctr, sizeof(ListCounters)));
+  SRS_TRY(ensure(W->totals, 4 * sizeof(uint64_t)));
+  return SRS_OK;
+}
 
-  // ---- descriptor: key view + columns (AoS records as <= 8-byte slices) --
-  SortDesc d;
-  memset(&d, 0, sizeof d);
-  key_masks(R.kind, R.up, d);
-  const bool is_float = R.kind == SRS_KEY_F32 || R.kind == SRS_KEY_F64;
-  d.canon_zero = (is_float && n <= R.thresh) ? 1 : 0;
-  d.leaf_skip = leaf_skip_of(R);
-  const int ksl = ks | (d.canon_zero ? SRS_KS_CANON : 0);  // kernel dispatch key
+// ---- the phases of run_sort, in the order it takes them ------
+
+// How the columns travel through the workspace, and which launch starts.
+struct Layout {
+  bool mid = false;        // the whole sort in one launch (launch_mid_sort)
+  bool mid1 = false;       // the first level in one launch (launch_mid_level)
+  bool aos_cols = false;   // AoS records as SoA slice columns in TMP / TMP2
+  bool pair_cols = false;  // two 4-byte payloads as one word column in TMP / TMP2
+  bool home_tmp2 = false;  // the scatters stay in TMP / TMP2, the local pass writes OUT
+  bool tmp2 = false;       // TMP2 is in use (SortDesc::tmp2)
+  size_t tmp_bytes = 0, slice_bytes = 0;
+  std::vector<size_t> tmp_off;  // the columns' places in TMP / TMP2
+};
+
+// Picks the layout and makes TMP (and TMP2) large enough for it.
+int choose_layout(Workspace* W, const Request& R, Layout* L) {
+  const int64_t n = R.num;
   // (the mid-size launch moves the columns as they are: no slices, no pairs)
-  const bool mid = R.nsegs == 0 && n > kLocalCap && n <= kMidMaxKeys && mid_enabled();
+  L->mid = R.nsegs == 0 && n > kLocalCap && n <= kMidMaxKeys && mid_enabled();
   // (above it, the first level in one launch; the layout is the general path's
   // except C2's interleaved pair words, which that launch's scatter does not write)
-  const bool mid1 = R.nsegs == 0 && n > kMidMaxKeys && n <= mid_level_max_n() && mid_enabled();
+  L->mid1 = R.nsegs == 0 && n > kMidMaxKeys && n <= mid_level_max_n() && mid_enabled();
+  const bool general = n > kLocalCap && R.nsegs == 0 && !L->mid;
 
   // AoS records of 16+ bytes travel as SoA slice columns through the
   // workspace (TMP, TMP2) between the first scatter and the local pass: the
   // later count passes then read 8-byte keys instead of whole records and
   // the middle scatters move dense columns
-  const bool aos_cols = R.aos && R.elem_size >= 16 && n > kLocalCap && R.nsegs == 0 && !mid;
+  L->aos_cols = R.aos && R.elem_size >= 16 && general;
   // A key and two 4-byte payload columns (C2) travel with the payloads
   // interleaved as one 8-byte word per record through TMP / TMP2: the
   // scatters then write 64-byte runs of words instead of two columns of
   // 32-byte runs (the same bytes as one 8-byte payload column measured
   // 23.6 -> 21.1 ms at 1e9)
-  const bool pair_cols = !R.aos && R.ncols == 3 && R.widths[1] == 4 && R.widths[2] == 4 &&
-                         n > kLocalCap && R.nsegs == 0 && !mid && !mid1;
+  L->pair_cols = !R.aos && R.ncols == 3 && R.widths[1] == 4 && R.widths[2] == 4 && general &&
+                 !L->mid1;
   // Home write (round 6): when the output columns are not placement-probed
   // memory (srs_alloc_device) -- the reference's in-place contract
   // (radixSort.hpp:1780) on the caller's own array, or any array of the
@@ -1812,113 +1416,100 @@ int run_sort(Workspace* W, const Request& R, hipStream_t st) {
   // contiguous run per segment. The scatter's partial 64-byte blocks are
   // what an unlucky placement slows down (6.2 vs 7.0 ms per
   // launch); a streaming write is far less exposed. (SRS_HOME_TMP2=0: off)
-  bool home_tmp2 = false;
-  if (!R.aos && !pair_cols && n >= kHomeTmp2MinN && R.nsegs == 0 && !mid && !mid1 &&
+  if (!R.aos && !L->pair_cols && n >= kHomeTmp2MinN && R.nsegs == 0 && !L->mid && !L->mid1 &&
       home_tmp2_enabled()) {
-    for (int c = 0; c < R.ncols && !home_tmp2; c++)
-      home_tmp2 = !placed_memory(R.out_cols[c], (size_t)n * R.widths[c]);
+    for (int c = 0; c < R.ncols && !L->home_tmp2; c++)
+      L->home_tmp2 = !placed_memory(R.out_cols[c], (size_t)n * R.widths[c]);
   }
-  size_t tmp_bytes = 0, slice_bytes = 0;
-  std::vector<size_t> tmp_off;
   if (R.aos) {
-    tmp_off.push_back(0);
-    slice_bytes = align_up((size_t)n * 8, 256);
-    tmp_bytes = aos_cols ? slice_bytes * (R.elem_size / 8) : align_up((size_t)n * R.elem_size, 256);
-  } else {
-    for (int c = 0; c < R.ncols; c++) {
-      tmp_off.push_back(tmp_bytes);
-      tmp_bytes += align_up((size_t)n * R.widths[c], 256);  // (a pair: 8n bytes at tmp_off[1])
-    }
+    L->tmp_off.push_back(0);
+    L->slice_bytes = align_up((size_t)n * 8, 256);
+    L->tmp_bytes = L->aos_cols ? L->slice_bytes * (R.elem_size / 8)
+                               : align_up((size_t)n * R.elem_size, 256);
+  } else {  // (a pair: 8n bytes at tmp_off[1])
+    L->tmp_bytes = col_offsets(n, R.ncols, R.widths, &L->tmp_off);
   }
-  SRS_TRY(ensure(W->tmp, tmp_bytes, ws_alloc_mode(), true));
-  char* tmp = (char*)W->tmp.p;
-  char* tmp2 = nullptr;
-  if (home_tmp2 && ensure(W->tmp2, tmp_bytes, ws_alloc_mode(), true) != SRS_OK) {
-    home_tmp2 = false;  // (no room for TMP2: the scatter writes OUT as before)
+  SRS_TRY(ensure(W->tmp, L->tmp_bytes, ws_alloc_mode(), true));
+  if (L->home_tmp2 && ensure(W->tmp2, L->tmp_bytes, ws_alloc_mode(), true) != SRS_OK) {
+    L->home_tmp2 = false;  // (no room for TMP2: the scatter writes OUT as before)
     (void)hipGetLastError();
   }
-  if (aos_cols || pair_cols || home_tmp2) {
-    SRS_TRY(ensure(W->tmp2, tmp_bytes, ws_alloc_mode(), true));
-    tmp2 = (char*)W->tmp2.p;
-    d.tmp2 = 1;
+  if (L->aos_cols || L->pair_cols || L->home_tmp2) {
+    SRS_TRY(ensure(W->tmp2, L->tmp_bytes, ws_alloc_mode(), true));
+    L->tmp2 = true;
   }
+  return SRS_OK;
+}
 
-  set_columns(R, d, tmp, tmp2, aos_cols, slice_bytes, tmp_off.data(), inplace, pair_cols);
-
-  d.stamp_acc = g_stamp_acc;
-  d.lb_status = g_lb_status;
-  d.lb_err = g_lb_err;
-  bool balanced = false, spread = false, ranges = false, ranges_final = false;
-  int lut_entries = 0, lut_mode = 1;
+// Plans the first level from the key sample and fills the descriptor's table
+// fields: a digit table, a range level (F->one_value: nothing to sort), or
+// neither.
+int plan_first_level(Workspace* W, const Request& R, SortDesc& d, hipStream_t st,
+                     FirstLevel* F) {
   std::vector<KeyCluster> clusters;
-  SRS_TRY(plan_balanced_level(W, R, d, &balanced, &lut_entries, &lut_mode, st, &spread,
-                              &clusters));
+  SRS_TRY(plan_balanced_level(W, R, d, st, F, &clusters));
   if (!clusters.empty()) {
-    bool one_value = false;
-    SRS_TRY(plan_range_level(W, R, clusters, d, st, &ranges, &ranges_final, &one_value));
-    if (one_value) return copy_through(R, st);  // (stable: nothing moves)
-    balanced = ranges;  // (the range level runs where a digit-table level would)
+    SRS_TRY(plan_range_level(W, R, clusters, d, st, F));
+    F->balanced = F->ranges;  // (the range level runs where a digit-table level would)
   }
-  if (balanced && !ranges) {
+  if (F->balanced && !F->ranges) {
     d.digit_lut = (const int32_t*)W->lut.p;
-    d.lut_shift = d.key_bits - (lut_mode == 3 ? 9 : 16);
-    d.lut_bits = lut_mode == 3 ? 9 : 16;
-    d.lut_mode = lut_mode;
-    d.lut_entries = lut_entries;
+    d.lut_shift = d.key_bits - (F->lut_mode == 3 ? 9 : 16);
+    d.lut_bits = F->lut_mode == 3 ? 9 : 16;
+    d.lut_mode = F->lut_mode;
+    d.lut_entries = F->lut_entries;
   }
-  SRS_TRY(ensure(W->desc, sizeof(SortDesc)));
-  SortDesc* d_desc = (SortDesc*)W->desc.p;
+  return SRS_OK;
+}
 
-  // ---- initial segments (the descriptor is written with them) --------------
-  const int home = inplace ? BUF_OUT : BUF_IN;
-  SRS_TRY(ensure(W->big[0], 1024 * sizeof(Seg)));
-  SRS_TRY(ensure(W->big[1], 1024 * sizeof(Seg)));
-  SRS_TRY(ensure(W->local, 1024 * sizeof(Seg)));
-  SRS_TRY(ensure(W->local2, 1024 * sizeof(Seg)));
-  SRS_TRY(ensure(W->copy, 1024 * sizeof(Seg)));
-  SRS_TRY(ensure(W->ctr, sizeof(ListCounters)));
-  SRS_TRY(ensure(W->totals, 4 * sizeof(uint64_t)));
+// What the later phases share: the call, its descriptor on both sides, the
+// kernels' dispatch key, the buffer the input lives in.
+struct SortRun {
+  Workspace* W;
+  const Request& R;
+  const SortDesc& d;
+  SortDesc* d_desc;
+  int ksl;
+  int home;
+  hipStream_t st;
+};
+
+// Caller segments (multi-GPU receive groups): sorted as sub-ranges of one
+// sort, each starting at the full key width (the varying-bit detection skips
+// what a segment's keys share).
+int start_segments(const SortRun& X, LevelState& S) {
+  Workspace* W = X.W;
+  const Request& R = X.R;
+  hipStream_t st = X.st;
+  std::vector<Seg> hb, hl, hl2;
+  uint64_t lel = 0;
+  for (int64_t i = 0; i < R.nsegs; i++) {
+    const int64_t a = R.seg_bounds[i], len = R.seg_bounds[i + 1] - a;
+    if (len < 2) continue;
+    const Seg g{a, len, X.d.key_bits - R.known_top_bits, X.home};
+    if (len <= kLocalCapSmall) hl.push_back(g);
+    else if (len <= kLocalCap) hl2.push_back(g);
+    else hb.push_back(g);
+    if (len <= kLocalCap) lel += (uint64_t)len;
+  }
+  SRS_TRY(ensure_lists(W, hb.size(), hl.size(), hl2.size()));
   ListCounters* d_ctr = (ListCounters*)W->ctr.p;
-  int64_t n_big = 0, n_local = 0, n_local2 = 0, n_copy = 0;
-  bool mid_continued = false;  // (the big list came from the mid-size launch)
-  int64_t one_seg_len = 0;     // (a segment sort of one large segment: its length)
-  if (R.nsegs > 0) {
-    // independent segments (multi-GPU receive groups): sorted as sub-ranges
-    // of one sort, each starting at the full key width (the varying-bit
-    // detection skips what a segment's keys share)
-    std::vector<Seg> hb, hl, hl2;
-    uint64_t lel = 0;
-    for (int64_t i = 0; i < R.nsegs; i++) {
-      const int64_t a = R.seg_bounds[i], len = R.seg_bounds[i + 1] - a;
-      if (len < 2) continue;
-      const Seg g{a, len, d.key_bits - R.known_top_bits, home};
-      if (len <= kLocalCapSmall) hl.push_back(g);
-      else if (len <= kLocalCap) hl2.push_back(g);
-      else hb.push_back(g);
-      if (len <= kLocalCap) lel += (uint64_t)len;
-    }
-    SRS_TRY(ensure(W->big[0], std::max<size_t>(1024, hb.size()) * sizeof(Seg)));
-    SRS_TRY(ensure(W->local, std::max<size_t>(1024, hl.size()) * sizeof(Seg)));
-    SRS_TRY(ensure(W->local2, std::max<size_t>(1024, hl2.size()) * sizeof(Seg)));
-    if (hb.size() == 1 && hl.empty() && hl2.empty()) {
-      // one large segment (the multi-GPU shard's rounds): the lists and the
-      // descriptor in one launch, no host copies and no host wait, and its
-      // first level sized from its length (no totals read-back): ~0.1 ms of
-      // stalls per round sort less
-      launch_start(d, d_desc, hb[0], 0, (Seg*)W->big[0].p, (Seg*)W->local.p, (Seg*)W->local2.p,
-                   d_ctr, st);
-      one_seg_len = hb[0].len;
-    } else {
-    if (!hb.empty())
-      HIP_TRY(hipMemcpyAsync(W->big[0].p, hb.data(), hb.size() * sizeof(Seg),
-                             hipMemcpyHostToDevice, st));
-    if (!hl.empty())
-      HIP_TRY(hipMemcpyAsync(W->local.p, hl.data(), hl.size() * sizeof(Seg),
-                             hipMemcpyHostToDevice, st));
-    if (!hl2.empty())
-      HIP_TRY(hipMemcpyAsync(W->local2.p, hl2.data(), hl2.size() * sizeof(Seg),
-                             hipMemcpyHostToDevice, st));
-    launch_set_desc(d, d_desc, st);
+  if (hb.size() == 1 && hl.empty() && hl2.empty()) {
+    // one large segment (the multi-GPU shard's rounds): the lists and the
+    // descriptor in one launch, no host copies and no host wait, and its
+    // first level sized from its length (no totals read-back): ~0.1 ms of
+    // stalls per round sort less
+    launch_start(X.d, X.d_desc, hb[0], 0, (Seg*)W->big[0].p, (Seg*)W->local.p,
+                 (Seg*)W->local2.p, d_ctr, st);
+    S.known_len = hb[0].len;
+  } else {
+    const std::pair<DevBuf*, std::vector<Seg>*> lists[] = {
+        {&W->big[0], &hb}, {&W->local, &hl}, {&W->local2, &hl2}};
+    for (auto& l : lists)
+      if (!l.second->empty())
+        HIP_TRY(hipMemcpyAsync(l.first->p, l.second->data(), l.second->size() * sizeof(Seg),
+                               hipMemcpyHostToDevice, st));
+    launch_set_desc(X.d, X.d_desc, st);
     ListCounters c;
     memset(&c, 0, sizeof c);
     c.n_big = hb.size();
@@ -1927,194 +1518,278 @@ int run_sort(Workspace* W, const Request& R, hipStream_t st) {
     c.local_elems = lel;
     HIP_TRY(hipMemcpyAsync(d_ctr, &c, sizeof c, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));  // the host vectors go out of scope
-    }
-    n_big = (int64_t)hb.size();
-    n_local = (int64_t)hl.size();
-    n_local2 = (int64_t)hl2.size();
-    W->h_ctr->local_elems = lel;
-  } else {
-    bool started = false;  // (by the mid-size launch)
-    if (mid) {
-      // one launch (grid barriers): the first level and every bucket's local
-      // sort; buckets over kLocalCap (skewed keys) come back in the big list
-      // and continue on the general levels below
-      const int64_t T = (n + kTile - 1) / kTile;
-      const int64_t part_bytes = mid_part_bytes(n);
-      SRS_TRY(ensure(W->mid, part_bytes + T * kMaxBins * sizeof(uint32_t)));
-      if (!W->midbar.p) {
-        SRS_TRY(ensure(W->midbar, mid_bar_words() * sizeof(unsigned long long)));
-        HIP_TRY(hipMemsetAsync(W->midbar.p, 0, mid_bar_words() * sizeof(unsigned long long), st));
-      }
-      auto barrier_failed = [&] { return __atomic_load_n(&W->h_mid->err, __ATOMIC_ACQUIRE) != 0; };
-      if (barrier_failed())  // (an earlier call's barrier timed out: its output was wrong)
-        return fail(SRS_ERR_INTERNAL, "mid-size launch: a grid barrier timed out");
-      DevBuf* tk = nullptr;
-      SRS_TRY(taken_slot(W, st, &tk));
-      DevBuf& taken = *tk;
-      hipError_t e;
-      const unsigned long long seq = ++W->mid_seq;
-      {
-        note_elems("mid", (double)n);
-        TimedScope ts("mid", (double)0, st);
-        e = launch_mid_sort(ksl, d, n, home, (unsigned long long*)W->mid.p,
-                            (uint32_t*)((char*)W->mid.p + part_bytes), d_ctr, (Seg*)W->big[0].p,
-                            (unsigned long long*)taken.p, W->h_mid, seq,
-                            (unsigned long long*)W->midbar.p, st);
-      }
-      if (e != hipSuccess) {
-        // (a grid the device cannot hold resident: the general path, which
-        // the column layout chosen for `mid` also serves)
-        (void)hipGetLastError();
-        if (trace_levels())
-          fprintf(stderr, "[srs] mid-size launch refused (%s): general path\n", hipGetErrorString(e));
-      } else {
-        // The kernel's workgroup 0 posts the big-bucket count to host memory
-        // once the first level's sizes are known (MidFlag): polled for a
-        // while (a stream sync's wake-up cost ~30 us per call), then waited for
-        SRS_TRY(wait_mid_flag(W->h_mid, seq, st));
-        if (barrier_failed())
-          return fail(SRS_ERR_INTERNAL, "mid-size launch: a grid barrier timed out");
-        const unsigned long long nb_flag = __atomic_load_n(&W->h_mid->n_big, __ATOMIC_ACQUIRE);
-        if (nb_flag >> 63)
-          return fail(SRS_ERR_INTERNAL, "mid-size launch: more buckets than workgroups");
-        n_big = (int64_t)nb_flag;
-        if (n_big == 0) {
-          W->last_small = true;  // (srs_debug_last_fallbacks reads `taken`)
-          W->last_small_stream = st;
-          return SRS_OK;
-        }
-        launch_set_desc(d, d_desc, st);
-        W->h_ctr->local_elems = 0;
-        started = true;
-      }
-    }
-    if (mid1) {
-      // the first level in one launch (grid barriers); the work lists and
-      // their lengths come back as after a general first level
-      const int64_t T = (n + kTile - 1) / kTile;
-      const int64_t part_bytes = mid_level_part_bytes();
-      SRS_TRY(ensure(W->mid, part_bytes + T * kMaxBins * sizeof(uint32_t)));
-      if (!W->midbar.p) {
-        SRS_TRY(ensure(W->midbar, mid_bar_words() * sizeof(unsigned long long)));
-        HIP_TRY(hipMemsetAsync(W->midbar.p, 0, mid_bar_words() * sizeof(unsigned long long), st));
-      }
-      auto barrier_failed = [&] { return __atomic_load_n(&W->h_mid->err, __ATOMIC_ACQUIRE) != 0; };
-      if (barrier_failed())
-        return fail(SRS_ERR_INTERNAL, "mid-size launch: a grid barrier timed out");
-      hipError_t e;
-      const unsigned long long seq = ++W->mid_seq;
-      {
-        note_elems("mid_level", (double)n);
-        TimedScope ts("mid_level", (double)0, st);
-        e = launch_mid_level(ksl, d, n, home, (unsigned long long*)W->mid.p,
-                             (uint32_t*)((char*)W->mid.p + part_bytes), d_ctr, (Seg*)W->big[0].p,
-                             (Seg*)W->local.p, (Seg*)W->local2.p, (Seg*)W->copy.p, d_desc,
-                             W->h_mid, seq, (unsigned long long*)W->midbar.p, st);
-      }
-      if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (trace_levels())
-          fprintf(stderr, "[srs] mid-level launch refused (%s): general path\n", hipGetErrorString(e));
-      } else {
-        SRS_TRY(wait_mid_flag(W->h_mid, seq, st));
-        if (barrier_failed())
-          return fail(SRS_ERR_INTERNAL, "mid-size launch: a grid barrier timed out");
-        n_big = (int64_t)__atomic_load_n(&W->h_mid->n_big, __ATOMIC_ACQUIRE);
-        n_local = (int64_t)__atomic_load_n(&W->h_mid->n_local, __ATOMIC_ACQUIRE);
-        n_local2 = (int64_t)__atomic_load_n(&W->h_mid->n_local2, __ATOMIC_ACQUIRE);
-        n_copy = (int64_t)__atomic_load_n(&W->h_mid->n_copy, __ATOMIC_ACQUIRE);
-        W->h_ctr->local_elems = __atomic_load_n(&W->h_mid->local_elems, __ATOMIC_ACQUIRE);
-        if (trace_levels())
-          fprintf(stderr, "[srs] mid-level: big %lld, local %lld, local2 %lld, copy %lld\n",
-                  (long long)n_big, (long long)n_local, (long long)n_local2, (long long)n_copy);
-        if (n_big + n_local + n_local2 + n_copy == 0) return SRS_OK;  // (keys all equal: copied)
-        started = true;
-      }
-    }
-    if (!started) {
-      Seg seg0{0, n, d.key_bits, home};
-      const bool to_local = n <= kLocalCap;
-      launch_start(d, d_desc, seg0, to_local ? 1 : 0, (Seg*)W->big[0].p, (Seg*)W->local.p,
-                   (Seg*)W->local2.p, d_ctr, st);
-      n_big = to_local ? 0 : 1;
-      n_local = (to_local && n <= kLocalCapSmall) ? 1 : 0;
-      n_local2 = (to_local && n > kLocalCapSmall) ? 1 : 0;
-      W->h_ctr->local_elems = to_local ? (uint64_t)n : 0;
-    } else {
-      mid_continued = true;
-    }
   }
-  LevelState S{n_big, n_local, n_local2, n_copy, 0, d.ncols, d.tmp2};
-  S.pair_tiles = pair_tiles_mode(d, ks, aos_cols);
-  if (R.nsegs == 0 && n_big == 1 && !mid_continued) S.known_len = n;
-  if (one_seg_len > 0) S.known_len = one_seg_len;
-  int level = 0;
-  // Stripe first level: large plain SoA sorts partition
-  // stripes of kStripeKeysPerBucket << b1 keys on their own with the first
-  // digit, so a tile's scattered runs land in its stripe's window (the
-  // second level's scatter, which writes into one bucket's window, measured
-  // 5.9 ms per C1 launch against 7.0 for the first one over the whole array)
+  S.nbig = (int64_t)hb.size();
+  S.n_local = (int64_t)hl.size();
+  S.n_local2 = (int64_t)hl2.size();
+  W->h_ctr->local_elems = lel;
+  return SRS_OK;
+}
+
+// The two one-launch starts (grid barriers) share the MidFlag protocol around
+// their launch. Before it: the tiles' scratch (part_bytes + a digit row per
+// tile), the barrier's words, this call's sequence number.
+bool mid_barrier_failed(const Workspace* W) {
+  return __atomic_load_n(&W->h_mid->err, __ATOMIC_ACQUIRE) != 0;
+}
+
+int mid_prepare(Workspace* W, int64_t n, int64_t part_bytes, hipStream_t st,
+                unsigned long long* seq) {
+  const int64_t T = (n + kTile - 1) / kTile;
+  SRS_TRY(ensure(W->mid, part_bytes + T * kMaxBins * sizeof(uint32_t)));
+  if (!W->midbar.p) {
+    SRS_TRY(ensure(W->midbar, mid_bar_words() * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(W->midbar.p, 0, mid_bar_words() * sizeof(unsigned long long), st));
+  }
+  if (mid_barrier_failed(W))  // (an earlier call's barrier timed out: its output was wrong)
+    return fail(SRS_ERR_INTERNAL, "mid-size launch: a grid barrier timed out");
+  *seq = ++W->mid_seq;
+  return SRS_OK;
+}
+
+// After it: *ran false when the launch was refused (a grid the device cannot
+// hold resident: the general path, which the column layout chosen for the
+// launch also serves). Else the kernel's workgroup 0 has posted the list
+// lengths to host memory once the first level's sizes were known (MidFlag):
+// polled for a while (a stream sync's wake-up cost ~30 us per call), then
+// waited for.
+int mid_answer(Workspace* W, hipError_t e, unsigned long long seq, const char* what,
+               hipStream_t st, bool* ran) {
+  *ran = e == hipSuccess;
+  if (!*ran) {
+    (void)hipGetLastError();
+    if (trace_levels())
+      fprintf(stderr, "[srs] %s launch refused (%s): general path\n", what, hipGetErrorString(e));
+    return SRS_OK;
+  }
+  SRS_TRY(wait_mid_flag(W->h_mid, seq, st));
+  if (mid_barrier_failed(W))
+    return fail(SRS_ERR_INTERNAL, "mid-size launch: a grid barrier timed out");
+  return SRS_OK;
+}
+
+// The mid-size launch: the first level and every bucket's local sort;
+// buckets over kLocalCap (skewed keys) come back in the big list and continue
+// on the general levels. *done: there were none, the sort is finished.
+int start_mid_sort(const SortRun& X, LevelState& S, bool* started, bool* done) {
+  Workspace* W = X.W;
+  hipStream_t st = X.st;
+  const int64_t n = X.R.num, part_bytes = mid_part_bytes(n);
+  unsigned long long seq = 0;
+  SRS_TRY(mid_prepare(W, n, part_bytes, st, &seq));
+  DevBuf* taken = nullptr;
+  SRS_TRY(taken_slot(W, st, &taken));
+  hipError_t e;
+  {
+    note_elems("mid", (double)n);
+    TimedScope ts("mid", (double)0, st);
+    e = launch_mid_sort(X.ksl, X.d, n, X.home, (unsigned long long*)W->mid.p,
+                        (uint32_t*)((char*)W->mid.p + part_bytes), (ListCounters*)W->ctr.p,
+                        (Seg*)W->big[0].p, (unsigned long long*)taken->p, W->h_mid, seq,
+                        (unsigned long long*)W->midbar.p, st);
+  }
+  bool ran = false;
+  SRS_TRY(mid_answer(W, e, seq, "mid-size", st, &ran));
+  if (!ran) return SRS_OK;
+  const unsigned long long nb_flag = __atomic_load_n(&W->h_mid->n_big, __ATOMIC_ACQUIRE);
+  if (nb_flag >> 63)
+    return fail(SRS_ERR_INTERNAL, "mid-size launch: more buckets than workgroups");
+  S.nbig = (int64_t)nb_flag;
+  if (S.nbig == 0) {
+    W->last_small = true;  // (srs_debug_last_fallbacks reads `taken`)
+    W->last_small_stream = st;
+    *done = true;
+    return SRS_OK;
+  }
+  launch_set_desc(X.d, X.d_desc, st);
+  W->h_ctr->local_elems = 0;
+  *started = true;
+  return SRS_OK;
+}
+
+// The first level in one launch; the work lists and their lengths come back
+// as after a general first level. *done: every list is empty (keys all
+// equal: copied).
+int start_mid_level(const SortRun& X, LevelState& S, bool* started, bool* done) {
+  Workspace* W = X.W;
+  hipStream_t st = X.st;
+  const int64_t n = X.R.num, part_bytes = mid_level_part_bytes();
+  unsigned long long seq = 0;
+  SRS_TRY(mid_prepare(W, n, part_bytes, st, &seq));
+  hipError_t e;
+  {
+    note_elems("mid_level", (double)n);
+    TimedScope ts("mid_level", (double)0, st);
+    e = launch_mid_level(X.ksl, X.d, n, X.home, (unsigned long long*)W->mid.p,
+                         (uint32_t*)((char*)W->mid.p + part_bytes), (ListCounters*)W->ctr.p,
+                         (Seg*)W->big[0].p, (Seg*)W->local.p, (Seg*)W->local2.p,
+                         (Seg*)W->copy.p, X.d_desc, W->h_mid, seq,
+                         (unsigned long long*)W->midbar.p, st);
+  }
+  bool ran = false;
+  SRS_TRY(mid_answer(W, e, seq, "mid-level", st, &ran));
+  if (!ran) return SRS_OK;
+  S.nbig = (int64_t)__atomic_load_n(&W->h_mid->n_big, __ATOMIC_ACQUIRE);
+  S.n_local = (int64_t)__atomic_load_n(&W->h_mid->n_local, __ATOMIC_ACQUIRE);
+  S.n_local2 = (int64_t)__atomic_load_n(&W->h_mid->n_local2, __ATOMIC_ACQUIRE);
+  S.n_copy = (int64_t)__atomic_load_n(&W->h_mid->n_copy, __ATOMIC_ACQUIRE);
+  W->h_ctr->local_elems = __atomic_load_n(&W->h_mid->local_elems, __ATOMIC_ACQUIRE);
+  if (trace_levels())
+    fprintf(stderr, "[srs] mid-level: big %lld, local %lld, local2 %lld, copy %lld\n",
+            (long long)S.nbig, (long long)S.n_local, (long long)S.n_local2, (long long)S.n_copy);
+  *done = S.nbig + S.n_local + S.n_local2 + S.n_copy == 0;
+  *started = !*done;
+  return SRS_OK;
+}
+
+// The plain start: the whole input as one segment, the lists and the
+// descriptor written by one launch. Its first level is sized from n (no
+// totals read-back).
+void start_plain(const SortRun& X, LevelState& S) {
+  Workspace* W = X.W;
+  const int64_t n = X.R.num;
+  Seg seg0{0, n, X.d.key_bits, X.home};
+  const bool to_local = n <= kLocalCap;
+  launch_start(X.d, X.d_desc, seg0, to_local ? 1 : 0, (Seg*)W->big[0].p, (Seg*)W->local.p,
+               (Seg*)W->local2.p, (ListCounters*)W->ctr.p, X.st);
+  S.nbig = to_local ? 0 : 1;
+  S.n_local = (to_local && n <= kLocalCapSmall) ? 1 : 0;
+  S.n_local2 = (to_local && n > kLocalCapSmall) ? 1 : 0;
+  W->h_ctr->local_elems = to_local ? (uint64_t)n : 0;
+  if (S.nbig == 1) S.known_len = n;
+}
+
+// The first work lists (the descriptor is written with them), from one of
+// four origins. S.known_len is set where the host knows the single big
+// segment's length: the plain start, and one large caller segment.
+int start_lists(const SortRun& X, const Layout& L, LevelState& S, bool* done) {
+  *done = false;
+  SRS_TRY(ensure_lists(X.W, 0, 0, 0));
+  if (X.R.nsegs > 0) return start_segments(X, S);
+  bool started = false;  // (by a one-launch start; else it was refused)
+  if (L.mid) SRS_TRY(start_mid_sort(X, S, &started, done));
+  if (L.mid1) SRS_TRY(start_mid_level(X, S, &started, done));
+  if (!started && !*done) start_plain(X, S);
+  return SRS_OK;
+}
+
+// Stripe first level: large plain SoA sorts partition
+// stripes of kStripeKeysPerBucket << b1 keys on their own with the first
+// digit, so a tile's scattered runs land in its stripe's window (the
+// second level's scatter, which writes into one bucket's window, measured
+// 5.9 ms per C1 launch against 7.0 for the first one over the whole array),
+// then the gathered level over the buckets. *ran: this sort took them.
+int run_stripe_levels(const SortRun& X, const FirstLevel& F, int ks, LevelState& S, bool* ran) {
+  Workspace* W = X.W;
+  hipStream_t st = X.st;
+  const int64_t n = X.R.num;
+  const int key_bits = X.d.key_bits;
   // (a balanced first level: its 512 digit-table groups are the buckets)
-  const int b1 = balanced ? kMaxDigitBits : choose_bits(n, d.key_bits);
+  const int b1 = F.balanced ? kMaxDigitBits : choose_bits(n, key_bits);
   const int64_t stripe_len = (int64_t)kStripeKeysPerBucket << b1;
   // Only when the first digit (or the digit table) spreads the keys: a
   // plain level skips a digit all keys share, a stripe level cannot (all-zero
   // keys: 9.4 ms plain, 17.7 ms with stripes), so the key sample decides.
-  const bool stripes = R.nsegs == 0 && !d.canon_zero && (ks == 4 || ks == 8) &&
-                       (balanced || spread) && !ranges_final &&
-                       n >= kStripeMinN && n < (int64_t(1) << 32) && n >= 2 * stripe_len &&
-                       stripes_enabled();
-  if (stripes) {
-    const int64_t K = (n + stripe_len - 1) / stripe_len;
-    std::vector<Seg> hs(K);
-    for (int64_t k = 0; k < K; k++)
-      hs[k] = Seg{k * stripe_len, std::min(stripe_len, n - k * stripe_len), d.key_bits, home};
-    SRS_TRY(ensure(W->big[0], K * sizeof(Seg)));
-    HIP_TRY(hipMemcpyAsync(W->big[0].p, hs.data(), K * sizeof(Seg), hipMemcpyHostToDevice, st));
-    const int nb = 1 << b1;
-    const size_t pieces = (size_t)K * kMaxBins;
-    SRS_TRY(ensure(W->prun, pieces * 4));
-    SRS_TRY(ensure(W->ptile, pieces * 4));
-    SRS_TRY(ensure(W->btot, kMaxBins * 8));
-    SRS_TRY(ensure(W->bnt, kMaxBins * 4));
-    SRS_TRY(ensure(W->btile, kMaxBins * 4));
-    SRS_TRY(ensure(W->nt_over, kMaxBins * 4));
-    // tiles of the gathered level: at most one partial tile per piece
-    SRS_TRY(ensure(W->gtile, ((n + kTile - 1) / kTile + (size_t)K * nb) * sizeof(GTile)));
-    W->gorder_cap = (n + kTile - 1) / kTile + (int64_t)K * nb;  // + K entries of scratch
-    SRS_TRY(ensure(W->gorder, (W->gorder_cap + K) * sizeof(int32_t)));
-    HIP_TRY(hipStreamSynchronize(st));  // hs goes out of scope
-    S.nbig = K;
-    S.known_len = -1;
-    LevelMode m1;
-    m1.mode = 1;
-    m1.key_bits = d.key_bits;
-    ++level;
-    if (balanced)
-      SRS_TRY(run_level(W, ksl, d_desc, S, kMaxDigitBits, d.lut_mode >= 2 ? 2 : 1, st,
-                        (const int32_t*)W->lut_rbits.p, m1));
-    else
-      SRS_TRY(run_level(W, ksl, d_desc, S, -b1, false, st, nullptr, m1));
-    LevelMode m2;
-    m2.mode = 2;
-    m2.gt = (const GTile*)W->gtile.p;
-    m2.nt_over = (const int32_t*)W->nt_over.p;
-    m2.torder = (const int32_t*)W->gorder.p;
-    ++level;
-    if (S.nbig > 0) SRS_TRY(run_level(W, ksl, d_desc, S, 0, false, st, nullptr, m2));
+  *ran = X.R.nsegs == 0 && !X.d.canon_zero && (ks == 4 || ks == 8) &&
+         (F.balanced || F.spread) && !F.ranges_final &&
+         n >= kStripeMinN && n < (int64_t(1) << 32) && n >= 2 * stripe_len &&
+         stripes_enabled();
+  if (!*ran) return SRS_OK;
+  const int64_t K = (n + stripe_len - 1) / stripe_len;
+  std::vector<Seg> hs(K);
+  for (int64_t k = 0; k < K; k++)
+    hs[k] = Seg{k * stripe_len, std::min(stripe_len, n - k * stripe_len), key_bits, X.home};
+  SRS_TRY(ensure(W->big[0], K * sizeof(Seg)));
+  HIP_TRY(hipMemcpyAsync(W->big[0].p, hs.data(), K * sizeof(Seg), hipMemcpyHostToDevice, st));
+  const int nb = 1 << b1;
+  const size_t pieces = (size_t)K * kMaxBins;
+  SRS_TRY(ensure(W->prun, pieces * 4));
+  SRS_TRY(ensure(W->ptile, pieces * 4));
+  SRS_TRY(ensure(W->btot, kMaxBins * 8));
+  SRS_TRY(ensure(W->bnt, kMaxBins * 4));
+  SRS_TRY(ensure(W->btile, kMaxBins * 4));
+  SRS_TRY(ensure(W->nt_over, kMaxBins * 4));
+  // tiles of the gathered level: at most one partial tile per piece
+  SRS_TRY(ensure(W->gtile, ((n + kTile - 1) / kTile + (size_t)K * nb) * sizeof(GTile)));
+  W->gorder_cap = (n + kTile - 1) / kTile + (int64_t)K * nb;  // + K entries of scratch
+  SRS_TRY(ensure(W->gorder, (W->gorder_cap + K) * sizeof(int32_t)));
+  HIP_TRY(hipStreamSynchronize(st));  // hs goes out of scope
+  S.nbig = K;
+  S.known_len = -1;
+  LevelSpec m1;
+  m1.stripe = STRIPE_LEVEL;
+  m1.key_bits = key_bits;
+  m1.bits = b1;
+  if (F.balanced) {
+    m1.table = X.d.lut_mode >= 2 ? TABLE_SMALL : TABLE_ANY;
+    m1.rbits = (const int32_t*)W->lut_rbits.p;
+  } else {
+    m1.plain = true;
   }
-  if (balanced && !stripes && S.nbig > 0) {
+  SRS_TRY(run_level(W, X.ksl, X.d_desc, S, st, m1));
+  if (S.nbig == 0) return SRS_OK;
+  LevelSpec m2;
+  m2.stripe = STRIPE_GATHERED;
+  m2.gt = (const GTile*)W->gtile.p;
+  m2.nt_over = (const int32_t*)W->nt_over.p;
+  m2.torder = (const int32_t*)W->gorder.p;
+  return run_level(W, X.ksl, X.d_desc, S, st, m2);
+}
+
+int run_sort(Workspace* W, const Request& R, hipStream_t st) {
+  if (R.nsegs == 0 && R.num <= kLocalCap) return run_small(W, R, st);
+  set_xcd_rotation(xcd_rotation_knob());
+  W->last_small = false;
+  const int ks = key_size_of(R.kind);
+  const bool inplace = is_inplace(R);
+
+  // ---- descriptor: key view + columns (AoS records as <= 8-byte slices) --
+  SortDesc d = init_desc(R.kind, R.up);
+  const bool is_float = R.kind == SRS_KEY_F32 || R.kind == SRS_KEY_F64;
+  d.canon_zero = (is_float && R.num <= R.thresh) ? 1 : 0;
+  d.leaf_skip = leaf_skip_of(R);
+  const int ksl = ks | (d.canon_zero ? SRS_KS_CANON : 0);  // kernel dispatch key
+  Layout L;
+  SRS_TRY(choose_layout(W, R, &L));
+  d.tmp2 = L.tmp2;
+  set_columns(R, d, (char*)W->tmp.p, L.tmp2 ? (char*)W->tmp2.p : nullptr, L.aos_cols,
+              L.slice_bytes, L.tmp_off.data(), inplace, L.pair_cols);
+  d.stamp_acc = g_stamp_acc;
+  d.lb_status = g_lb_status;
+  d.lb_err = g_lb_err;
+
+  // ---- the first level's plan (key sample: digit table, ranges, stripes) ----
+  FirstLevel F;
+  SRS_TRY(plan_first_level(W, R, d, st, &F));
+  if (F.one_value) return copy_through(R, st);  // (stable: nothing moves)
+  SRS_TRY(ensure(W->desc, sizeof(SortDesc)));
+  const SortRun X{W, R, d, (SortDesc*)W->desc.p, ksl, inplace ? BUF_OUT : BUF_IN, st};
+
+  // ---- the first work lists ---------------------------------------------------
+  LevelState S{0, 0, 0, 0, 0, d.ncols, d.tmp2};
+  bool done = false;
+  SRS_TRY(start_lists(X, L, S, &done));
+  if (done) return SRS_OK;
+  S.pair_tiles = pair_tiles_mode(d, ks, L.aos_cols);
+
+  // ---- the levels: stripe pair or table level, then general levels ------------
+  bool stripes = false;
+  SRS_TRY(run_stripe_levels(X, F, ks, S, &stripes));
+  int level = stripes ? 2 : 0;
+  if (F.balanced && !stripes && S.nbig > 0) {
     ++level;
-    LevelMode m0;
-    m0.home = ranges_final;  // (single-valued buckets: written home directly)
-    SRS_TRY(run_level(W, ksl, d_desc, S, kMaxDigitBits, d.lut_mode >= 2 ? 2 : 1, st,
-                      (const int32_t*)W->lut_rbits.p, m0));
+    LevelSpec m0;
+    m0.bits = kMaxDigitBits;
+    m0.table = d.lut_mode >= 2 ? TABLE_SMALL : TABLE_ANY;
+    m0.rbits = (const int32_t*)W->lut_rbits.p;
+    m0.home = F.ranges_final;  // (single-valued buckets: written home directly)
+    SRS_TRY(run_level(W, ksl, X.d_desc, S, st, m0));
   }
   while (S.nbig > 0) {
     if (++level > 80) return fail(SRS_ERR_INTERNAL, "level limit exceeded");
-    SRS_TRY(run_level(W, ksl, d_desc, S, 0, false, st));
+    SRS_TRY(run_level(W, ksl, X.d_desc, S, st));
   }
-  return run_lists_tail(W, R, d, d_desc, S.n_local, S.n_local2, S.n_copy, aos_cols, st);
+  return run_lists_tail(W, R, d, X.d_desc, S.n_local, S.n_local2, S.n_copy, L.aos_cols, st);
 }
 
 // The end of every sort that went through the work lists: the LDS chain over
@@ -2249,9 +1924,7 @@ int run_partition(Workspace* W, const Request& R, int bits, const int32_t* d_lut
   W->last_small = false;  // (srs_debug_last_fallbacks then reports this call's counters)
   const int ks = key_size_of(R.kind);
   const int64_t n = R.num;
-  SortDesc d;
-  memset(&d, 0, sizeof d);
-  key_masks(R.kind, R.up, d);
+  SortDesc d = init_desc(R.kind, R.up);
   for (int c = 0; c < R.ncols; c++) {
     char* in = (char*)R.in_cols[c];
     char* out = (char*)R.out_cols[c];
@@ -2279,23 +1952,20 @@ int run_partition(Workspace* W, const Request& R, int bits, const int32_t* d_lut
   if (aligned) d.digit_lut = nullptr;
   SRS_TRY(ensure(W->desc, sizeof(SortDesc)));
   SortDesc* d_desc = (SortDesc*)W->desc.p;
-  SRS_TRY(ensure(W->big[0], 1024 * sizeof(Seg)));
-  SRS_TRY(ensure(W->big[1], 1024 * sizeof(Seg)));
-  SRS_TRY(ensure(W->local, 1024 * sizeof(Seg)));
-  SRS_TRY(ensure(W->local2, 1024 * sizeof(Seg)));
-  SRS_TRY(ensure(W->copy, 1024 * sizeof(Seg)));
-  SRS_TRY(ensure(W->ctr, sizeof(ListCounters)));
-  SRS_TRY(ensure(W->totals, 4 * sizeof(uint64_t)));
+  SRS_TRY(ensure_lists(W, 0, 0, 0));
   Seg seg0{0, n, d.key_bits, BUF_IN};
   launch_start(d, d_desc, seg0, 0, (Seg*)W->big[0].p, (Seg*)W->local.p, (Seg*)W->local2.p,
                (ListCounters*)W->ctr.p, st);
-  int fb = 1;
-  while ((1 << fb) < nparts) fb++;
+  const int fb = fb0;
   LevelState S{1, 0, 0, 0, 0, d.ncols, 0};
   // the plain-digit partition takes the tile-pair scatter like a sort's
   // levels (C1 chunks: 6.6 -> ~5.9 ms per 1e9 keys)
   if (aligned && partition_pairs_enabled()) S.pair_tiles = pair_tiles_mode(d, ks, false);
-  SRS_TRY(run_level(W, ks, d_desc, S, aligned ? -fb : fb, aligned ? 0 : 1, st));
+  LevelSpec part;  // one forced digit of fb bits: plain, or through the caller's table
+  part.bits = fb;
+  part.plain = aligned;
+  part.table = aligned ? TABLE_NONE : TABLE_ANY;
+  SRS_TRY(run_level(W, ks, d_desc, S, st, part));
   // group sizes from the segment's bucket bases (sbase row 0)
   std::vector<uint64_t> sb((size_t)1 << fb);
   HIP_TRY(hipMemcpyAsync(sb.data(), W->sbase.p, sb.size() * 8, hipMemcpyDeviceToHost, st));
@@ -2339,14 +2009,13 @@ bool whole_input_is_unsorted_leaf(const Request& R) {
 
 int sort_device(Request& R, hipStream_t st) {
   if (R.num <= 1 || whole_input_is_unsorted_leaf(R)) return copy_through(R, st);
-  Workspace* W = nullptr;
-  WsLock lk;
-  SRS_TRY(acquire_ws(&W, &lk));
-  // (a small sort touches no workspace buffer but its stream's debug slot)
-  if (R.num <= kLocalCap) return run_small(W, R, st);
-  WsUse use;
-  SRS_TRY(use.begin(W, st));
-  return run_sort(W, R, st);
+  WsScope ws;
+  SRS_TRY(ws.lock());
+  // (a small sort touches no workspace buffer but its stream's debug slot:
+  // the lock, but no place in the workspace's stream order)
+  if (R.num <= kLocalCap) return run_small(ws.W, R, st);
+  SRS_TRY(ws.begin(st));
+  return run_sort(ws.W, R, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -2367,10 +2036,7 @@ std::atomic<int64_t> g_topk_candidates{kTopkCandidates};
 constexpr int64_t kTopkFullPercent = 50;
 // (SRS_TOPK_FULL_PCT overrides the percentage, for crossover measurements:
 // tools/topk_bench.py; read on every call)
-int64_t topk_full_percent() {
-  const char* e = getenv("SRS_TOPK_FULL_PCT");
-  return (e && *e) ? atoll(e) : kTopkFullPercent;
-}
+int64_t topk_full_percent() { return knob_int("SRS_TOPK_FULL_PCT", kTopkFullPercent); }
 
 // The columns a top-k call moves, with their views in the input and in the
 // caller's output: SoA columns as they are; an AoS record as its key and the
@@ -2415,6 +2081,13 @@ int sort_locked(Workspace* W, const Request& R, hipStream_t st) {
   return run_sort(W, R, st);
 }
 
+// The gather's descriptor (W->seldesc): d's first nc columns, the key first.
+void set_gather_desc(Workspace* W, SortDesc& d, int nc, hipStream_t st) {
+  d.key = d.cols[0];
+  d.ncols = nc;
+  launch_set_desc(d, (SortDesc*)W->seldesc.p, st);
+}
+
 // (under the caller's workspace lock and WsUse)
 int topk_locked(Workspace* W, const Request& R, int64_t k, int64_t* idx_out, hipStream_t st) {
   const int64_t n = R.num;
@@ -2429,9 +2102,7 @@ int topk_locked(Workspace* W, const Request& R, int64_t k, int64_t* idx_out, hip
   }
   TopkLayout L;
   topk_layout(R, L);
-  SortDesc kd;
-  memset(&kd, 0, sizeof kd);
-  key_masks(R.kind, R.up, kd);
+  SortDesc kd = init_desc(R.kind, R.up);
   SelectArgs a;
   memset(&a, 0, sizeof a);
   a.keys = L.in[0];
@@ -2543,15 +2214,11 @@ int topk_locked(Workspace* W, const Request& R, int64_t k, int64_t* idx_out, hip
     for (int c = 0; c < nsc; c++) F.out_cols[c] = S.out_cols[c];
     SRS_TRY(sort_locked(W, F, st));
   } else {
-    SortDesc d;
-    memset(&d, 0, sizeof d);
-    key_masks(R.kind, R.up, d);
+    SortDesc d = init_desc(R.kind, R.up);
     for (int c = 0; c < L.nc; c++)
       d.cols[c] = Col{{L.in[c], sel + off[c], nullptr, nullptr}, L.width[c],
                       {L.stride[c], L.width[c], L.width[c], L.width[c]}};
-    d.key = d.cols[0];
-    d.ncols = L.nc;
-    launch_set_desc(d, (SortDesc*)W->seldesc.p, st);
+    set_gather_desc(W, d, L.nc, st);
     const uint64_t* tbase = nullptr;
     if (!full) {
       const int64_t ntiles = (n + kTile - 1) / kTile;
@@ -2576,17 +2243,13 @@ int topk_locked(Workspace* W, const Request& R, int64_t k, int64_t* idx_out, hip
   }
 
   // ---- the first k records to the caller's arrays ----------------------------
-  SortDesc d;
-  memset(&d, 0, sizeof d);
-  key_masks(R.kind, R.up, d);
+  SortDesc d = init_desc(R.kind, R.up);
   for (int c = 0; c < nsc; c++) {
     const uint32_t w = S.widths[c];
     char* out = c < L.nc ? L.out[c] : (char*)idx_out;
     d.cols[c] = Col{{sel + off[c], out, nullptr, nullptr}, w, {w, c < L.nc ? L.stride[c] : 8u, w, w}};
   }
-  d.key = d.cols[0];
-  d.ncols = nsc;
-  launch_set_desc(d, (SortDesc*)W->seldesc.p, st);
+  set_gather_desc(W, d, nsc, st);
   SelectArgs f = a;
   f.keys = sel;
   f.stride = (uint32_t)ks;
@@ -2601,12 +2264,9 @@ int topk_locked(Workspace* W, const Request& R, int64_t k, int64_t* idx_out, hip
 }
 
 int topk_device(const Request& R, int64_t k, int64_t* idx_out, hipStream_t st) {
-  Workspace* W = nullptr;
-  WsLock lk;
-  SRS_TRY(acquire_ws(&W, &lk));
-  WsUse use;
-  SRS_TRY(use.begin(W, st));
-  return topk_locked(W, R, k, idx_out, st);
+  WsScope ws;
+  SRS_TRY(ws.begin(st));
+  return topk_locked(ws.W, R, k, idx_out, st);
 }
 
 bool ranges_overlap(const void* a, size_t an, const void* b, size_t bn) {
@@ -2614,29 +2274,59 @@ bool ranges_overlap(const void* a, size_t an, const void* b, size_t bn) {
   return an && bn && x < y + bn && y < x + an;
 }
 
-// What the top-k entry points check after the request is built, all before
-// the first device access: NULL arrays, alignment, outputs clear of inputs.
-int topk_validate(const Request& R, int64_t k, const void* out0, const int64_t* idx_out) {
-  const int64_t kk = std::min(k, R.num);
-  if (!R.in_cols[0]) return fail(SRS_ERR_INVALID_ARG, R.aos ? "elements is NULL" : "keys is NULL");
-  if (!out0) return fail(SRS_ERR_INVALID_ARG, R.aos ? "elements_out is NULL" : "keys_out is NULL");
+// What the device entry points check of their arrays, all before the first
+// device access. Device columns are read and written as whole 1/2/4/8-byte
+// words, so every device pointer must be aligned to its word (hipMalloc and
+// torch allocations always are); host arrays may be unaligned, as in the
+// reference (loadu, src/simd.hpp): they are staged through HBM.
+// what NULL (the sorts, which may run in place): alignment only. Else (the
+// out-of-place calls, "top-k" / "sort rows"): the column count with
+// indices_out; then, unless out_recs <= 0 (the call will do nothing), the
+// caller's shape error if any, NULL arrays, alignment (rows: the row-wise
+// calls' message), and the outputs' out_recs records clear of the inputs'
+// in_recs.
+int validate_outputs(const Request& R, const char* what = nullptr, const void* out0 = nullptr,
+                     const int64_t* idx_out = nullptr, int64_t in_recs = 0, int64_t out_recs = 0,
+                     bool rows = false, const char* shape_err = nullptr) {
+  if (what) {
+    if (idx_out && !R.aos && R.ncols - 1 > SRS_MAX_PAYLOADS - 1)
+      return fail(SRS_ERR_UNSUPPORTED,
+                  "indices_out travels as one more payload column: at most 63 payload columns "
+                  "with it");
+    if (out_recs <= 0) return SRS_OK;
+    if (shape_err) return fail(SRS_ERR_INVALID_ARG, shape_err);
+    if (!R.in_cols[0]) return fail(SRS_ERR_INVALID_ARG, R.aos ? "elements is NULL" : "keys is NULL");
+    if (!out0) return fail(SRS_ERR_INVALID_ARG, R.aos ? "elements_out is NULL" : "keys_out is NULL");
+  }
   for (int c = 0; c < R.ncols; c++) {
-    if (!R.in_cols[c] || !R.out_cols[c]) return fail(SRS_ERR_INVALID_ARG, "payload pointer is NULL");
+    if (what && (!R.in_cols[c] || !R.out_cols[c]))
+      return fail(SRS_ERR_INVALID_ARG, "payload pointer is NULL");
     const uint32_t al = R.aos ? (R.elem_size < 8 ? R.elem_size : 8) : R.widths[c];
     if (((uintptr_t)R.in_cols[c] | (uintptr_t)R.out_cols[c]) % al != 0)
-      return fail(SRS_ERR_INVALID_ARG, "device arrays must be aligned to their element size "
-                                       "(records: to min(elem_size, 8))");
+      return fail(SRS_ERR_INVALID_ARG,
+                  rows ? "device arrays must be aligned to their element size"
+                       : "device arrays must be aligned to their element size "
+                         "(records: to min(elem_size, 8))");
   }
+  if (!what) return SRS_OK;
   if ((uintptr_t)idx_out % 8 != 0) return fail(SRS_ERR_INVALID_ARG, "indices_out must be 8-byte aligned");
   for (int o = 0; o <= R.ncols; o++) {
     const void* op = o < R.ncols ? R.out_cols[o] : (const void*)idx_out;
-    const size_t ob = (size_t)kk * (o < R.ncols ? R.widths[o] : 8);
+    const size_t ob = (size_t)out_recs * (o < R.ncols ? R.widths[o] : 8);
     if (!op) continue;
     for (int c = 0; c < R.ncols; c++)
-      if (ranges_overlap(op, ob, R.in_cols[c], (size_t)R.num * R.widths[c]))
-        return fail(SRS_ERR_INVALID_ARG, "top-k outputs must not overlap the inputs");
+      if (ranges_overlap(op, ob, R.in_cols[c], (size_t)in_recs * R.widths[c]))
+        return fail(SRS_ERR_INVALID_ARG,
+                    std::string(what) + " outputs must not overlap the inputs");
   }
   return SRS_OK;
+}
+
+// (the sorts: nothing to check of num <= 1 records)
+int check_device_alignment(const Request& R) { return R.num <= 1 ? SRS_OK : validate_outputs(R); }
+
+int topk_validate(const Request& R, int64_t k, const void* out0, const int64_t* idx_out) {
+  return validate_outputs(R, "top-k", out0, idx_out, R.num, std::min(k, R.num));
 }
 
 // ---------------------------------------------------------------------------
@@ -2664,29 +2354,14 @@ bool topk_rows_prefers_loop(int64_t rows, int64_t row_len) {
 // row-wise sort validates through this too, with kk = row_len)
 int topk_rows_validate(const Request& R, int64_t rows, int64_t row_stride, int64_t kk,
                        const void* out0, const int64_t* idx_out, const char* what = "top-k") {
-  if (row_stride < R.num) return fail(SRS_ERR_INVALID_ARG, "row_stride < row_len");
+  const bool work = rows > 0 && R.num > 0 && kk > 0;
   int64_t cells = 0;
-  if (__builtin_mul_overflow(rows, row_stride, &cells) || cells > (INT64_MAX >> 4))
-    return fail(SRS_ERR_INVALID_ARG, "rows * row_stride overflows");
-  if (!R.in_cols[0]) return fail(SRS_ERR_INVALID_ARG, "keys is NULL");
-  if (!out0) return fail(SRS_ERR_INVALID_ARG, "keys_out is NULL");
-  for (int c = 0; c < R.ncols; c++) {
-    if (!R.in_cols[c] || !R.out_cols[c]) return fail(SRS_ERR_INVALID_ARG, "payload pointer is NULL");
-    if (((uintptr_t)R.in_cols[c] | (uintptr_t)R.out_cols[c]) % R.widths[c] != 0)
-      return fail(SRS_ERR_INVALID_ARG, "device arrays must be aligned to their element size");
-  }
-  if ((uintptr_t)idx_out % 8 != 0) return fail(SRS_ERR_INVALID_ARG, "indices_out must be 8-byte aligned");
-  const size_t in_recs = (size_t)((rows - 1) * row_stride + R.num), out_recs = (size_t)(rows * kk);
-  for (int o = 0; o <= R.ncols; o++) {
-    const void* op = o < R.ncols ? R.out_cols[o] : (const void*)idx_out;
-    const size_t ob = out_recs * (o < R.ncols ? R.widths[o] : 8);
-    if (!op) continue;
-    for (int c = 0; c < R.ncols; c++)
-      if (ranges_overlap(op, ob, R.in_cols[c], in_recs * R.widths[c]))
-        return fail(SRS_ERR_INVALID_ARG,
-                    std::string(what) + " outputs must not overlap the inputs");
-  }
-  return SRS_OK;
+  const char* shape = row_stride < R.num ? "row_stride < row_len"
+                      : __builtin_mul_overflow(rows, row_stride, &cells) || cells > (INT64_MAX >> 4)
+                          ? "rows * row_stride overflows"
+                          : nullptr;
+  if (!work || shape) return validate_outputs(R, what, out0, idx_out, 0, work, true, shape);
+  return validate_outputs(R, what, out0, idx_out, (rows - 1) * row_stride + R.num, rows * kk, true);
 }
 
 // The one-launch routes' kernel (launch_topk_rows): the first kk records of
@@ -2696,9 +2371,7 @@ int launch_rows_kernel(DevBuf& pass, const Request& R, int64_t rows, int64_t row
                        int64_t kk, int64_t* idx_out, bool stream, hipStream_t st) {
   SRS_TRY(ensure(pass, sizeof(unsigned long long)));
   HIP_TRY(hipMemsetAsync(pass.p, 0, sizeof(unsigned long long), st));
-  SortDesc kd;
-  memset(&kd, 0, sizeof kd);
-  key_masks(R.kind, R.up, kd);
+  SortDesc kd = init_desc(R.kind, R.up);
   TopkRowsArgs a;
   memset(&a, 0, sizeof a);
   a.rows = rows;
@@ -2737,11 +2410,9 @@ int topk_rows_device(const Request& R, int64_t rows, int64_t row_stride, int64_t
                 "top-k rows: the stream route takes 8192 < row_len < 2^31 and min(k, row_len) <= "
                 "kTopkRowsMaxK");
   }
-  Workspace* W = nullptr;
-  WsLock lk;
-  SRS_TRY(acquire_ws(&W, &lk));
-  WsUse use;
-  SRS_TRY(use.begin(W, st));
+  WsScope ws;
+  SRS_TRY(ws.begin(st));
+  Workspace* W = ws.W;
   int64_t* info = W->topk_rows_info;
   info[0] = route;
   info[1] = info[2] = info[3] = 0;
@@ -2808,16 +2479,10 @@ int sort_rows_lists(Workspace* W, const Request& Q, int64_t rows, int64_t row_le
   const int64_t n = Q.num;
   const bool inplace = is_inplace(Q);
   const bool levels = row_len > kLocalCap;
-  SortDesc d;
-  memset(&d, 0, sizeof d);
-  key_masks(Q.kind, Q.up, d);  // (threshold 0: canon_zero and leaf_skip stay 0)
+  SortDesc d = init_desc(Q.kind, Q.up);  // (threshold 0: canon_zero and leaf_skip stay 0)
   // the levels scatter through TMP; the LDS chain alone touches IN and OUT only
-  size_t tmp_bytes = 0;
   std::vector<size_t> tmp_off;
-  for (int c = 0; c < Q.ncols; c++) {
-    tmp_off.push_back(tmp_bytes);
-    tmp_bytes += align_up((size_t)n * Q.widths[c], 256);
-  }
+  const size_t tmp_bytes = col_offsets(n, Q.ncols, Q.widths, &tmp_off);
   char* tmp = nullptr;
   if (levels) {
     SRS_TRY(ensure(W->tmp, tmp_bytes, ws_alloc_mode(), true));
@@ -2832,14 +2497,7 @@ int sort_rows_lists(Workspace* W, const Request& Q, int64_t rows, int64_t row_le
 
   // ---- the lists: one segment per row, all in one list ----------------------
   const int cls = levels ? 2 : row_len > kLocalCapSmall ? 1 : 0;
-  const size_t cap = (size_t)std::max<int64_t>(1024, rows) * sizeof(Seg);
-  SRS_TRY(ensure(W->big[0], cls == 2 ? cap : 1024 * sizeof(Seg)));
-  SRS_TRY(ensure(W->big[1], 1024 * sizeof(Seg)));
-  SRS_TRY(ensure(W->local, cls == 0 ? cap : 1024 * sizeof(Seg)));
-  SRS_TRY(ensure(W->local2, cls == 1 ? cap : 1024 * sizeof(Seg)));
-  SRS_TRY(ensure(W->copy, 1024 * sizeof(Seg)));
-  SRS_TRY(ensure(W->ctr, sizeof(ListCounters)));
-  SRS_TRY(ensure(W->totals, 4 * sizeof(uint64_t)));
+  SRS_TRY(ensure_lists(W, cls == 2 ? rows : 0, cls == 0 ? rows : 0, cls == 1 ? rows : 0));
   ListCounters* d_ctr = (ListCounters*)W->ctr.p;
   Seg* list = (Seg*)(cls == 2 ? W->big[0].p : cls == 1 ? W->local2.p : W->local.p);
   launch_set_desc(d, d_desc, st);
@@ -2855,7 +2513,7 @@ int sort_rows_lists(Workspace* W, const Request& Q, int64_t rows, int64_t row_le
   while (S.nbig > 0) {
     if (++level > 80) return fail(SRS_ERR_INTERNAL, "level limit exceeded");
     *readbacks += (S.nbig == 1 && S.known_len >= 0) ? 1 : 2;  // (totals, counters)
-    SRS_TRY(run_level(W, ks, d_desc, S, 0, false, st));
+    SRS_TRY(run_level(W, ks, d_desc, S, st));
   }
   return run_lists_tail(W, Q, d, d_desc, S.n_local, S.n_local2, S.n_copy, false, st);
 }
@@ -2877,11 +2535,9 @@ int sort_rows_device(const Request& R, int64_t rows, int64_t row_stride, int64_t
   } else if (route == SORT_ROWS_LEVELS && len <= kLocalCap) {
     return fail(SRS_ERR_UNSUPPORTED, "sort rows: the levels take row_len > 8192");
   }
-  Workspace* W = nullptr;
-  WsLock lk;
-  SRS_TRY(acquire_ws(&W, &lk));
-  WsUse use;
-  SRS_TRY(use.begin(W, st));
+  WsScope ws;
+  SRS_TRY(ws.begin(st));
+  Workspace* W = ws.W;
   int64_t* info = W->sort_rows_info;
   info[0] = route;
   info[1] = info[2] = info[3] = 0;
@@ -2946,7 +2602,7 @@ constexpr size_t kPackedMaxBytes = size_t(256) << 10;       // below: all column
 constexpr size_t kZeroCopyMaxBytes = size_t(2) << 20;       // below: kernels on host memory
 size_t stage_min_bytes() {  // (SRS_STAGE_MIN_MB overrides, for experiments)
   static const size_t v = [] {
-    const char* e = getenv("SRS_STAGE_MIN_MB");
+    const char* e = knob_str("SRS_STAGE_MIN_MB");
     return e && *e ? (size_t)atoll(e) << 20 : kStageMinBytesDefault;
   }();
   return v;
@@ -3095,8 +2751,6 @@ struct DeviceGuard {
   }
 };
 
-size_t col_width(const Request& R, int c) { return R.aos ? R.elem_size : R.widths[c]; }
-
 // One device: every column staged into HBM (W->stage), sorted there in
 // place, copied back.
 int host_sort_single(Request& R, int dev) {
@@ -3109,12 +2763,8 @@ int host_sort_single(Request& R, int dev) {
   Workspace* W = nullptr;
   WsLock lk;
   SRS_TRY(acquire_ws(&W, &lk));
-  std::vector<size_t> off;
-  size_t total = 0;
-  for (int c = 0; c < R.ncols; c++) {
-    off.push_back(total);
-    total += align_up((size_t)R.num * col_width(R, c), 256);
-  }
+  std::vector<size_t> off;  // (AoS: widths[0] is the record size)
+  const size_t total = col_offsets(R.num, R.ncols, R.widths, &off);
   hipStream_t st = S->st;
   WsUse use;
   SRS_TRY(use.begin(W, st));
@@ -3125,13 +2775,13 @@ int host_sort_single(Request& R, int dev) {
     // themselves (no DMA commands: a small or mid-size sort's PCIe round
     // trips cost less than two copy launches and their waits)
     for (int c = 0; c < R.ncols; c++) {
-      memcpy(S->zc + off[c], R.in_cols[c], (size_t)R.num * col_width(R, c));
+      memcpy(S->zc + off[c], R.in_cols[c], (size_t)R.num * R.widths[c]);
       D.in_cols[c] = D.out_cols[c] = S->zc + off[c];
     }
     SRS_TRY(run_sort(W, D, st));
     SRS_TRY(sync_poll(st));
     for (int c = 0; c < R.ncols; c++)
-      memcpy(R.out_cols[c], S->zc + off[c], (size_t)R.num * col_width(R, c));
+      memcpy(R.out_cols[c], S->zc + off[c], (size_t)R.num * R.widths[c]);
     return SRS_OK;
   }
   SRS_TRY(ensure(W->stage, total));
@@ -3143,23 +2793,23 @@ int host_sort_single(Request& R, int dev) {
     // the pageable / staged paths, which overlap the host copy with the DMA.
     char* pin = S->pin[0][0];
     for (int c = 0; c < R.ncols; c++)
-      memcpy(pin + off[c], R.in_cols[c], (size_t)R.num * col_width(R, c));
+      memcpy(pin + off[c], R.in_cols[c], (size_t)R.num * R.widths[c]);
     HIP_TRY(hipMemcpyAsync(W->stage.p, pin, total, hipMemcpyHostToDevice, st));
     SRS_TRY(run_sort(W, D, st));
     HIP_TRY(hipMemcpyAsync(pin, W->stage.p, total, hipMemcpyDeviceToHost, st));
     SRS_TRY(sync_poll(st));
     for (int c = 0; c < R.ncols; c++)
-      memcpy(R.out_cols[c], pin + off[c], (size_t)R.num * col_width(R, c));
+      memcpy(R.out_cols[c], pin + off[c], (size_t)R.num * R.widths[c]);
     return SRS_OK;
   }
   for (int c = 0; c < R.ncols; c++)
     SRS_TRY(staged_copy(S, (char*)D.in_cols[c], (char*)R.in_cols[c],
-                        (size_t)R.num * col_width(R, c), true));
+                        (size_t)R.num * R.widths[c], true));
   SRS_TRY(run_sort(W, D, st));
   SRS_TRY(sync_poll(st));
   for (int c = 0; c < R.ncols; c++)
     SRS_TRY(staged_copy(S, (char*)D.out_cols[c], (char*)R.out_cols[c],
-                        (size_t)R.num * col_width(R, c), false));
+                        (size_t)R.num * R.widths[c], false));
   return SRS_OK;
 }
 
@@ -3184,7 +2834,7 @@ std::vector<int> host_devices() {
   std::lock_guard<std::mutex> g(g_hdmu);
   if (!g_host_devs_set) {
     g_host_devs_set = true;
-    const char* e = getenv("SRS_HOST_DEVICES");  // "all" or "0,1,2,3"
+    const char* e = knob_str("SRS_HOST_DEVICES");  // "all" or "0,1,2,3"
     if (e && *e) {
       int ndev = 0;
       if (!strcmp(e, "all")) {
@@ -3255,9 +2905,7 @@ int host_sort_split(Request& R, const std::vector<int>& devs) {
   const int ks = key_size_of(R.kind);
   const int bits = std::min(kSplitBits, 8 * ks);
   const int nbins = 1 << bits;
-  SortDesc dm;
-  memset(&dm, 0, sizeof dm);
-  key_masks(R.kind, R.up, dm);
+  SortDesc dm = init_desc(R.kind, R.up);
   std::vector<int64_t> lo(G + 1);
   for (int g = 0; g <= G; g++) lo[g] = n * g / G;
   int64_t maxchunk = 0;
@@ -3272,12 +2920,8 @@ int host_sort_split(Request& R, const std::vector<int>& devs) {
     HIP_TRY(hipSetDevice(devs[g]));
     SRS_TRY(get_stage(devs[g], &S[g]));
     std::lock_guard<std::mutex> slk(S[g]->mu);
-    std::vector<size_t> off(R.ncols + 1);
-    size_t t = 0;
-    for (int c = 0; c < R.ncols; c++) {
-      off[c] = t;
-      t += align_up((size_t)maxchunk * R.widths[c], 256);
-    }
+    std::vector<size_t> off;
+    const size_t t = col_offsets(maxchunk, R.ncols, R.widths, &off);
     SRS_TRY(ensure(B[g]->in, t));
     SRS_TRY(ensure(B[g]->part, t));
     SRS_TRY(ensure(B[g]->hist, nbins * sizeof(uint64_t)));
@@ -3324,12 +2968,8 @@ int host_sort_split(Request& R, const std::vector<int>& devs) {
     SRS_TRY(ensure(B[g]->lut, nbins * sizeof(int32_t)));
     HIP_TRY(hipMemcpyAsync(B[g]->lut.p, lut.data(), nbins * sizeof(int32_t),
                            hipMemcpyHostToDevice, st));
-    std::vector<size_t> off(R.ncols);
-    size_t t = 0;
-    for (int c = 0; c < R.ncols; c++) {
-      off[c] = t;
-      t += align_up((size_t)maxchunk * R.widths[c], 256);
-    }
+    std::vector<size_t> off;
+    col_offsets(maxchunk, R.ncols, R.widths, &off);
     Request P = R;
     P.num = m;
     for (int c = 0; c < R.ncols; c++) {
@@ -3379,14 +3019,9 @@ int host_sort_split(Request& R, const std::vector<int>& devs) {
     const int64_t m = rtot[h];
     if (m == 0) return SRS_OK;
     hipStream_t st = S[h]->st;
-    std::vector<size_t> roff(R.ncols), poff(R.ncols);
-    size_t t = 0, tp = 0;
-    for (int c = 0; c < R.ncols; c++) {
-      roff[c] = t;
-      t += align_up((size_t)m * R.widths[c], 256);
-      poff[c] = tp;
-      tp += align_up((size_t)maxchunk * R.widths[c], 256);
-    }
+    std::vector<size_t> roff, poff;
+    const size_t t = col_offsets(m, R.ncols, R.widths, &roff);
+    col_offsets(maxchunk, R.ncols, R.widths, &poff);
     SRS_TRY(ensure(B[h]->recv, t));
     Request D = R;
     D.num = m;
@@ -3481,21 +3116,6 @@ int build_soa(Request& R, int64_t num, int kind, int up, int64_t thresh, void* k
   return SRS_OK;
 }
 
-// Device columns are read and written as whole 1/2/4/8-byte words, so every
-// device pointer must be aligned to its word (hipMalloc and torch
-// allocations always are). Host arrays may be unaligned, as in the reference
-// (loadu, src/simd.hpp): they are staged through HBM.
-int check_device_alignment(const Request& R) {
-  if (R.num <= 1) return SRS_OK;
-  for (int c = 0; c < R.ncols; c++) {
-    const uint32_t a = R.aos ? (R.elem_size < 8 ? R.elem_size : 8) : R.widths[c];
-    if (((uintptr_t)R.in_cols[c] | (uintptr_t)R.out_cols[c]) % a != 0)
-      return fail(SRS_ERR_INVALID_ARG, "device arrays must be aligned to their element size "
-                                       "(records: to min(elem_size, 8))");
-  }
-  return SRS_OK;
-}
-
 int build_aos(Request& R, int64_t num, int kind, int up, int64_t thresh, void* elems,
               uint32_t esz, void* elems_out) {
   SRS_TRY(validate_common(num, kind));
@@ -3549,8 +3169,8 @@ int64_t release_deferred_frees() {
 // message is posted, so that no rank can fail an allocation (or wait in one)
 // once its peers depend on it (srs_shard.hip).
 int reserve_segments_workspace(int64_t num, int ncols, const uint32_t* widths) {
-  size_t tmp_bytes = 0;
-  for (int c = 0; c < ncols; c++) tmp_bytes += align_up((size_t)std::max<int64_t>(num, 1) * widths[c], 256);
+  std::vector<size_t> off;
+  const size_t tmp_bytes = col_offsets(std::max<int64_t>(num, 1), ncols, widths, &off);
   Workspace* W = nullptr;
   WsLock lk;
   SRS_TRY(acquire_ws(&W, &lk));
@@ -3566,17 +3186,14 @@ extern "C" {
 
 int srs_sort_soa(int64_t num, int key_kind, int up, int64_t cmp_sort_threshold, void* keys,
                  int32_t num_payloads, void* const* payloads, const uint32_t* payload_sizes) {
-  Request R;
-  SRS_TRY(build_soa(R, num, key_kind, up, cmp_sort_threshold, keys, num_payloads, payloads,
-                    payload_sizes, nullptr, nullptr));
-  return sort_host(R);
+  return srs_sort_soa_leaf(num, key_kind, up, cmp_sort_threshold, SRS_LEAF_SORTED, keys,
+                           num_payloads, payloads, payload_sizes);
 }
 
 int srs_sort_aos(int64_t num, int key_kind, int up, int64_t cmp_sort_threshold,
                  void* elements, uint32_t elem_size) {
-  Request R;
-  SRS_TRY(build_aos(R, num, key_kind, up, cmp_sort_threshold, elements, elem_size, nullptr));
-  return sort_host(R);
+  return srs_sort_aos_leaf(num, key_kind, up, cmp_sort_threshold, SRS_LEAF_SORTED, elements,
+                           elem_size);
 }
 
 int srs_sort_soa_leaf(int64_t num, int key_kind, int up, int64_t cmp_sort_threshold,
@@ -3624,11 +3241,9 @@ int srs_sort_soa_device(int64_t num, int key_kind, int up, int64_t cmp_sort_thre
                         void* keys, int32_t num_payloads, void* const* payloads,
                         const uint32_t* payload_sizes, void* keys_out,
                         void* const* payloads_out, void* stream) {
-  Request R;
-  SRS_TRY(build_soa(R, num, key_kind, up, cmp_sort_threshold, keys, num_payloads, payloads,
-                    payload_sizes, keys_out, payloads_out));
-  SRS_TRY(check_device_alignment(R));
-  return sort_device(R, (hipStream_t)stream);
+  return srs_sort_soa_device_leaf(num, key_kind, up, cmp_sort_threshold, SRS_LEAF_SORTED, keys,
+                                  num_payloads, payloads, payload_sizes, keys_out, payloads_out,
+                                  stream);
 }
 
 int srs_sort_segments_device(int64_t num, int key_kind, int up, void* keys,
@@ -3652,22 +3267,16 @@ int srs_sort_segments_device(int64_t num, int key_kind, int up, void* keys,
   R.seg_bounds = segment_bounds;
   R.nsegs = num_segments;
   R.known_top_bits = known_top_bits;
-  Workspace* W = nullptr;
-  WsLock lk;
-  SRS_TRY(acquire_ws(&W, &lk));
-  WsUse use;
-  SRS_TRY(use.begin(W, (hipStream_t)stream));
-  return run_sort(W, R, (hipStream_t)stream);
+  WsScope ws;
+  SRS_TRY(ws.begin((hipStream_t)stream));
+  return run_sort(ws.W, R, (hipStream_t)stream);
 }
 
 int srs_sort_aos_device(int64_t num, int key_kind, int up, int64_t cmp_sort_threshold,
                         void* elements, uint32_t elem_size, void* elements_out,
                         void* stream) {
-  Request R;
-  SRS_TRY(build_aos(R, num, key_kind, up, cmp_sort_threshold, elements, elem_size,
-                    elements_out));
-  SRS_TRY(check_device_alignment(R));
-  return sort_device(R, (hipStream_t)stream);
+  return srs_sort_aos_device_leaf(num, key_kind, up, cmp_sort_threshold, SRS_LEAF_SORTED,
+                                  elements, elem_size, elements_out, stream);
 }
 
 int srs_topk_soa_device(int64_t num, int64_t k, int key_kind, int up, const void* keys,
@@ -3677,12 +3286,8 @@ int srs_topk_soa_device(int64_t num, int64_t k, int key_kind, int up, const void
   Request R;
   SRS_TRY(build_soa(R, num, key_kind, up, 0, (void*)keys, num_payloads, (void* const*)payloads,
                     payload_sizes, keys_out, payloads_out));
-  if (indices_out && num_payloads > SRS_MAX_PAYLOADS - 1)
-    return fail(SRS_ERR_UNSUPPORTED,
-                "indices_out travels as one more payload column: at most 63 payload columns "
-                "with it");
-  if (k <= 0 || num <= 0) return SRS_OK;
   SRS_TRY(topk_validate(R, k, keys_out, indices_out));
+  if (k <= 0 || num <= 0) return SRS_OK;
   return topk_device(R, k, indices_out, (hipStream_t)stream);
 }
 
@@ -3694,12 +3299,8 @@ int srs_topk_rows_soa_device(int64_t rows, int64_t row_len, int64_t row_stride, 
   Request R;
   SRS_TRY(build_soa(R, row_len, key_kind, up, 0, (void*)keys, num_payloads,
                     (void* const*)payloads, payload_sizes, keys_out, payloads_out));
-  if (indices_out && num_payloads > SRS_MAX_PAYLOADS - 1)
-    return fail(SRS_ERR_UNSUPPORTED,
-                "indices_out travels as one more payload column: at most 63 payload columns "
-                "with it");
-  if (rows <= 0 || row_len <= 0 || k <= 0) return SRS_OK;
   SRS_TRY(topk_rows_validate(R, rows, row_stride, std::min(k, row_len), keys_out, indices_out));
+  if (rows <= 0 || row_len <= 0 || k <= 0) return SRS_OK;
   return topk_rows_device(R, rows, row_stride, k, indices_out, (hipStream_t)stream);
 }
 
@@ -3711,12 +3312,8 @@ int srs_sort_rows_soa_device(int64_t rows, int64_t row_len, int64_t row_stride, 
   Request R;
   SRS_TRY(build_soa(R, row_len, key_kind, up, 0, (void*)keys, num_payloads,
                     (void* const*)payloads, payload_sizes, keys_out, payloads_out));
-  if (indices_out && num_payloads > SRS_MAX_PAYLOADS - 1)
-    return fail(SRS_ERR_UNSUPPORTED,
-                "indices_out travels as one more payload column: at most 63 payload columns "
-                "with it");
-  if (rows <= 0 || row_len <= 0) return SRS_OK;
   SRS_TRY(topk_rows_validate(R, rows, row_stride, row_len, keys_out, indices_out, "sort rows"));
+  if (rows <= 0 || row_len <= 0) return SRS_OK;
   return sort_rows_device(R, rows, row_stride, indices_out, (hipStream_t)stream);
 }
 
@@ -3725,8 +3322,8 @@ int srs_topk_aos_device(int64_t num, int64_t k, int key_kind, int up, const void
                         void* stream) {
   Request R;
   SRS_TRY(build_aos(R, num, key_kind, up, 0, (void*)elements, elem_size, elements_out));
-  if (k <= 0 || num <= 0) return SRS_OK;
   SRS_TRY(topk_validate(R, k, elements_out, indices_out));
+  if (k <= 0 || num <= 0) return SRS_OK;
   return topk_device(R, k, indices_out, (hipStream_t)stream);
 }
 
@@ -3769,9 +3366,7 @@ int srs_key_histogram_device(int64_t num, int key_kind, int up, const void* keys
   if (!keys || !hist) return fail(SRS_ERR_INVALID_ARG, "NULL pointer");
   if ((uintptr_t)keys % ks != 0 || (uintptr_t)hist % 8 != 0)
     return fail(SRS_ERR_INVALID_ARG, "device arrays must be aligned to their element size");
-  SortDesc d;
-  memset(&d, 0, sizeof d);
-  key_masks(key_kind, up, d);
+  SortDesc d = init_desc(key_kind, up);
   launch_key_hist(ks, num, keys, d, bits, (unsigned long long*)hist, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return SRS_OK;
@@ -3799,9 +3394,7 @@ int srs_partition_device(int64_t num, int key_kind, int up, const void* keys,
   if (num == 1) {
     // a single key: its group from the table, then a plain copy
     int32_t one = 0;
-    SortDesc d;
-    memset(&d, 0, sizeof d);
-    key_masks(key_kind, up, d);
+    SortDesc d = init_desc(key_kind, up);
     uint64_t bitsv = 0;
     HIP_TRY(hipMemcpy(&bitsv, keys, ks, hipMemcpyDeviceToHost));
     uint64_t u = bitsv ^ ((bitsv & d.signbit) ? d.mneg : d.mpos);
@@ -3810,12 +3403,9 @@ int srs_partition_device(int64_t num, int key_kind, int up, const void* keys,
     part_counts[one] = 1;
     return copy_through(R, (hipStream_t)stream);
   }
-  Workspace* W = nullptr;
-  WsLock lk;
-  SRS_TRY(acquire_ws(&W, &lk));
-  WsUse use;
-  SRS_TRY(use.begin(W, (hipStream_t)stream));
-  return run_partition(W, R, bits, part_of_bucket, num_parts, part_counts, (hipStream_t)stream);
+  WsScope ws;
+  SRS_TRY(ws.begin((hipStream_t)stream));
+  return run_partition(ws.W, R, bits, part_of_bucket, num_parts, part_counts, (hipStream_t)stream);
 }
 
 const char* srs_last_error(void) { return g_err.c_str(); }
@@ -3878,31 +3468,31 @@ int srs_debug_set_lookback(void* status, void* err) {
   return SRS_OK;
 }
 
-int srs_debug_last_local_counts(int64_t* counts) {
-  if (!counts) return fail(SRS_ERR_INVALID_ARG, "counts is NULL");
-  Workspace* W = nullptr;
-  WsLock lk;
-  SRS_TRY(acquire_ws(&W, &lk));
-  counts[0] = counts[1] = 0;
+// The last call's list counters, once the device is idle; zeros when that
+// call was a single-launch sort or nothing has run (W locked by the caller).
+static int last_counters(Workspace* W, ListCounters* c) {
+  memset(c, 0, sizeof *c);
   if (W->last_small || !W->ctr.p) return SRS_OK;
   HIP_TRY(hipDeviceSynchronize());
-  ListCounters c;
-  HIP_TRY(hipMemcpy(&c, W->ctr.p, sizeof c, hipMemcpyDeviceToHost));
-  counts[0] = (int64_t)(c.n_local + c.n_local2);
-  counts[1] = (int64_t)(c.n_redo + c.n_redo2);
+  HIP_TRY(hipMemcpy(c, W->ctr.p, sizeof *c, hipMemcpyDeviceToHost));
+  return SRS_OK;
+}
+
+int srs_debug_last_local_counts(int64_t* counts) {
+  if (!counts) return fail(SRS_ERR_INVALID_ARG, "counts is NULL");
+  int64_t cls[4];
+  SRS_TRY(srs_debug_last_local_classes(cls));
+  counts[0] = cls[0] + cls[1];
+  counts[1] = cls[2] + cls[3];
   return SRS_OK;
 }
 
 int srs_debug_last_local_classes(int64_t* counts) {
   if (!counts) return fail(SRS_ERR_INVALID_ARG, "counts is NULL");
-  Workspace* W = nullptr;
-  WsLock lk;
-  SRS_TRY(acquire_ws(&W, &lk));
-  counts[0] = counts[1] = counts[2] = counts[3] = 0;
-  if (W->last_small || !W->ctr.p) return SRS_OK;
-  HIP_TRY(hipDeviceSynchronize());
+  WsScope ws;
+  SRS_TRY(ws.lock());
   ListCounters c;
-  HIP_TRY(hipMemcpy(&c, W->ctr.p, sizeof c, hipMemcpyDeviceToHost));
+  SRS_TRY(last_counters(ws.W, &c));
   counts[0] = (int64_t)c.n_local;
   counts[1] = (int64_t)c.n_local2;
   counts[2] = (int64_t)c.n_redo;
@@ -3927,10 +3517,8 @@ int srs_debug_last_fallbacks(int64_t* counts) {
                       hipMemcpyDeviceToHost));
     return SRS_OK;
   }
-  if (!W->ctr.p) return SRS_OK;
-  HIP_TRY(hipDeviceSynchronize());
   ListCounters c;
-  HIP_TRY(hipMemcpy(&c, W->ctr.p, sizeof c, hipMemcpyDeviceToHost));
+  SRS_TRY(last_counters(W, &c));
   counts[0] = (int64_t)(c.n_fallback + c.n_fallback1);
   counts[1] = (int64_t)c.n_fallback2;
   return SRS_OK;
@@ -3943,7 +3531,7 @@ int srs_debug_plan_table(const uint32_t* hist, int64_t num, int key_bits, int32_
     return fail(SRS_ERR_INVALID_ARG, "srs_debug_plan_table: arguments");
   std::vector<uint32_t> h(hist, hist + 65536);
   TablePlan P;
-  plan_table(h, num, key_bits, &P);
+  plan_table(h, num, key_bits, table_knob(), &P);
   *mode = P.mode;
   if (groups) *groups = P.groups;
   if (overflow) *overflow = P.over;

@@ -7,7 +7,8 @@ for spec in "$@"; do
   name=${spec%%:*}; flags=${spec#*:}
   out=lib/variants/$name; rm -rf $out build/v_$name; mkdir -p $out build/v_$name
   pids=()
-  for f in srs_kernels srs_api srs_shard; do
+  for src in csrc/*.hip; do  # (every unit of the work tree; they see csrc/*.h)
+    f=$(basename $src .hip)
     /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -munsafe-fp-atomics $flags \
       -Rpass-analysis=kernel-resource-usage -c csrc/$f.hip -o build/v_$name/$f.o 2> build/v_$name/$f.remarks &
     pids+=($!)
