@@ -335,6 +335,36 @@ void sort_rows(void* stream, const SortIndex rows, const SortIndex row_len,
                 "device::sort_rows");
 }
 
+// sort_ragged: every segment [offsets[i], offsets[i + 1]) of dense arrays of
+// num records sorted in one call, out of place (srs_sort_ragged_soa_device).
+// offsets: num_segments + 1 non-decreasing int64 values in DEVICE memory,
+// within [0, num]; record j of segment i's stable sort lands at
+// [offsets[i] + j] of keys_out and of every payload_out. The second form
+// also writes every record's position inside its segment to indices_out.
+template <bool Up = true, typename K, typename... Ps>
+void sort_ragged(void* stream, const SortIndex num, const SortIndex num_segments,
+                 const int64_t* const offsets, const K* const keys, K* const keys_out,
+                 int64_t* const indices_out, std::pair<const Ps*, Ps*>... payloads) {
+  static_assert(detail::key_kind<K>() >= 0, "unsupported key type");
+  static_assert((detail::valid_payload<Ps> && ...), "payload sizes must be 1, 2, 4 or 8");
+  static_assert(sizeof...(Ps) <= SRS_MAX_PAYLOADS, "too many payload arrays");
+  const void* pays[sizeof...(Ps) + 1] = {(const void*)payloads.first..., nullptr};
+  void* pays_out[sizeof...(Ps) + 1] = {(void*)payloads.second..., nullptr};
+  uint32_t sizes[sizeof...(Ps) + 1] = {(uint32_t)sizeof(Ps)..., 0};
+  detail::check(srs_sort_ragged_soa_device((int64_t)num, (int64_t)num_segments, offsets,
+                                           detail::key_kind<K>(), Up ? 1 : 0, (const void*)keys,
+                                           (int32_t)sizeof...(Ps), pays, sizes, (void*)keys_out,
+                                           pays_out, indices_out, stream),
+                "device::sort_ragged");
+}
+template <bool Up = true, typename K, typename... Ps>
+void sort_ragged(void* stream, const SortIndex num, const SortIndex num_segments,
+                 const int64_t* const offsets, const K* const keys, K* const keys_out,
+                 std::pair<const Ps*, Ps*>... payloads) {
+  sort_ragged<Up>(stream, num, num_segments, offsets, keys, keys_out, (int64_t*)nullptr,
+                  payloads...);
+}
+
 }  // namespace device
 }  // namespace radix_sort
 }  // namespace simd_sort

@@ -255,6 +255,46 @@ int srs_sort_rows_soa_device(int64_t rows, int64_t row_len, int64_t row_stride,
                              void* keys_out, void* const* payloads_out,
                              int64_t* indices_out, void* stream);
 
+/* Ragged sort: segments given by a DEVICE array of offsets, every segment
+ * sorted in one call, out of place. offsets holds num_segments + 1 int64
+ * values in device memory, non-decreasing, with 0 <= offsets[0] and
+ * offsets[num_segments] <= num; segment i is records [offsets[i],
+ * offsets[i + 1]) of every column. Columns are dense and num records long;
+ * the outputs have the inputs' shape: record j of segment i's result is at
+ * offsets[i] + j of every *_out column. Each segment's result is the stable
+ * sort by transformed key (equal keys keep their input order; floats in the
+ * total order at every length, -0.0 before +0.0; NaN keys are outside the
+ * contract; up == 0 reverses the key order), bit-equal to
+ * srs_sort_rows_soa_device when the offsets are uniform. indices_out (may be
+ * NULL) receives positions inside the segment, 0 .. len - 1; it travels as
+ * one more 8-byte column, so 64 payload columns with indices return
+ * SRS_ERR_UNSUPPORTED. The inputs and offsets are never written, and records
+ * outside [offsets[0], offsets[num_segments]) are neither read nor written
+ * in the outputs. Empty segments are legal; a segment of one record is
+ * copied (index 0). There is no in-place form: every output must be clear of
+ * every input column and of the offsets (srs_sort_segments_device stays the
+ * in-place call, with host bounds).
+ * Checked before any device access: key_kind, payload sizes, NULL or
+ * misaligned pointers (offsets: 8-byte aligned), num_segments + 1
+ * overflowing, and any output (indices included) over any input column or
+ * the offsets array. num <= 0 or num_segments <= 0 is a no-op.
+ * Bad offsets (a decreasing pair, a negative start, an end beyond num) are
+ * seen on the device only: no kernel of the call reads or writes a column
+ * outside [0, num) whatever offsets holds, a segment with a bad bound is
+ * skipped and counted, and when the count comes back non-zero the call
+ * returns SRS_ERR_INVALID_ARG (srs_last_error() names the count); the
+ * outputs are then unspecified.
+ * Host waits: ONE pinned read-back of the segment counters after the
+ * classify pass (segments of at most 256 records are sorted by a kernel
+ * queued behind that copy, a wave per segment, and never wait for it); after
+ * that, only what the sort's global levels need for segments of more than
+ * 8192 records, two read-backs a level. */
+int srs_sort_ragged_soa_device(int64_t num, int64_t num_segments, const int64_t* offsets,
+                               int key_kind, int up, const void* keys, int32_t num_payloads,
+                               const void* const* payloads, const uint32_t* payload_sizes,
+                               void* keys_out, void* const* payloads_out,
+                               int64_t* indices_out, void* stream);
+
 /* ---- multi-GPU shard primitives (top-radix-bits partition) --
  * A node-wide sort of one array spread over N GPUs: every rank histograms
  * its keys' top bits (srs_key_histogram_device), the histograms are summed
@@ -550,6 +590,20 @@ int srs_debug_set_sort_rows_route(int route);
  * not counted), info[2] = host read-backs during the call, info[3] = 1 if the
  * prepare pass ran (strided rows or an index column made dense). */
 int srs_debug_last_sort_rows(int64_t* info);
+
+/* Test hook, process-wide: the longest segment srs_sort_ragged_soa_device
+ * leaves to its wave-per-segment kernel. -1: the default (256); 0: that
+ * kernel is off (no launch, every segment of >= 1 record takes the work
+ * lists); 1 .. 256: the maximum. Anything else returns SRS_ERR_INVALID_ARG.
+ * Needs no device. */
+int srs_debug_set_sort_ragged_short_max(int32_t len);
+
+/* What the last ragged sort on the current device did (host state only: no
+ * synchronization): info[0] = segments left to the short kernel
+ * (num_segments - listed - empty - bad), info[1] / info[2] / info[3] = the
+ * small-class / large-class / big list lengths as first read back, info[4] =
+ * host read-backs during the call, info[5] = 1 if the prepare pass ran. */
+int srs_debug_last_sort_ragged(int64_t* info);
 
 #ifdef __cplusplus
 }

@@ -605,6 +605,9 @@ struct Workspace {
   // that the top-k hook's stays that call's); what the last call did
   DevBuf sortrowspass;
   int64_t sort_rows_info[4] = {0, 0, 0, 0};
+  // ragged sort: what the last call did; the event behind its counter copy
+  int64_t sort_ragged_info[6] = {0, 0, 0, 0, 0, 0};
+  hipEvent_t ev_ragged = nullptr;
   hipStream_t side = nullptr;  // medium sorts: the large local class's stream
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   ListCounters* h_ctr = nullptr;
@@ -650,6 +653,7 @@ struct Workspace {
     if (side) (void)hipStreamDestroy(side);
     if (ev_fork) (void)hipEventDestroy(ev_fork);
     if (ev_join) (void)hipEventDestroy(ev_join);
+    if (ev_ragged) (void)hipEventDestroy(ev_ragged);
     (void)hipGetLastError();  // (release-time failures leave no sticky error behind)
   }
 };
@@ -2580,6 +2584,145 @@ int sort_rows_device(const Request& R, int64_t rows, int64_t row_stride, int64_t
 }
 
 // ---------------------------------------------------------------------------
+// ragged sort: segments [offsets[i], offsets[i + 1]) of dense
+// columns, the offsets on the device. One classify pass (ragged_segs_kernel)
+// lists the segments longer than short_max and counts the bad and the empty
+// ones; its counters come back through W->h_ctr while the short kernel, which
+// owns every segment of 1 .. short_max records, is already queued behind the
+// copy. Listed segments then run the sort's levels and LDS chain exactly as
+// the rows of sort_rows_lists do.
+// ---------------------------------------------------------------------------
+std::atomic<int> g_sort_ragged_short_max{-1};  // srs_debug_set_sort_ragged_short_max
+
+// Host wait for an event with sync_poll's manners.
+int event_poll(hipEvent_t ev) {
+  const auto t0 = std::chrono::steady_clock::now();
+  for (;;) {
+    const hipError_t q = hipEventQuery(ev);
+    if (q == hipSuccess) return SRS_OK;
+    if (q != hipErrorNotReady) HIP_TRY(q);
+    const auto dt = std::chrono::steady_clock::now() - t0;
+    if (dt > std::chrono::milliseconds(20)) break;
+    if (dt < std::chrono::microseconds(200)) cpu_relax();
+    else std::this_thread::yield();
+  }
+  HIP_TRY(hipEventSynchronize(ev));
+  return SRS_OK;
+}
+
+// What ragged_segs_kernel and run_lists_tail may index of the lists: valid
+// offsets list at most num / (short_max + 1) segments, the kernel lists no
+// more than that of any others.
+int64_t ragged_list_cap(int64_t num, int64_t nseg, int short_max) {
+  return std::min(nseg, num / ((int64_t)short_max + 1));
+}
+
+// R: the dense columns (R.num = num records each).
+int sort_ragged_device(const Request& R, int64_t nseg, const int64_t* offsets, int64_t* idx_out,
+                       hipStream_t st) {
+  int short_max = g_sort_ragged_short_max.load();
+  if (short_max < 0) short_max = kRowsWaveMax;
+  const int64_t num = R.num;
+  const int64_t cap = ragged_list_cap(num, nseg, short_max);
+  if ((nseg + 255) / 256 > 0x7fffffff)
+    return fail(SRS_ERR_UNSUPPORTED, "sort ragged: more than 2^39 segments");
+  WsScope ws;
+  SRS_TRY(ws.begin(st));
+  Workspace* W = ws.W;
+  W->last_small = false;
+  int64_t* info = W->sort_ragged_info;
+  for (int i = 0; i < 6; i++) info[i] = 0;
+  const int ks = key_size_of(R.kind);
+  const bool with_idx = idx_out != nullptr;
+  SortDesc d = init_desc(R.kind, R.up);  // (threshold 0: canon_zero and leaf_skip stay 0)
+
+  RaggedArgs a;
+  memset(&a, 0, sizeof a);
+  a.num = num;
+  a.nseg = nseg;
+  a.offsets = offsets;
+  a.ncols = R.ncols;
+  a.key_bits = d.key_bits;
+  a.mpos = d.mpos;
+  a.mneg = d.mneg;
+  a.short_max = short_max;
+  a.idx_out = idx_out;
+  for (int c = 0; c < R.ncols; c++)
+    a.col[c] = TopkRowsCol{(const char*)R.in_cols[c], (char*)R.out_cols[c], R.widths[c]};
+
+  // ---- classify, and the one read-back of the counters ----------------------
+  SRS_TRY(ensure_lists(W, (size_t)cap, (size_t)cap, (size_t)cap));
+  ListCounters* d_ctr = (ListCounters*)W->ctr.p;
+  if (!W->ev_ragged) HIP_TRY(hipEventCreateWithFlags(&W->ev_ragged, hipEventDisableTiming));
+  HIP_TRY(hipMemsetAsync(d_ctr, 0, sizeof(ListCounters), st));
+  {
+    TimedScope ts("ragged_segs", (double)nseg, st);
+    HIP_TRY(launch_ragged_segs(offsets, nseg, num, short_max, d.key_bits,
+                               with_idx ? BUF_OUT : BUF_IN, cap, (Seg*)W->big[0].p,
+                               (Seg*)W->local.p, (Seg*)W->local2.p, (Seg*)W->copy.p, d_ctr, st));
+  }
+  HIP_TRY(hipMemcpyAsync(W->h_ctr, d_ctr, sizeof(ListCounters), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipEventRecord(W->ev_ragged, st));
+  if (short_max > 0) {
+    // (queued behind the copy, so the host's wait below does not include it)
+    TimedScope ts("ragged_short", (double)num, st);
+    HIP_TRY(launch_ragged_short(ks, a, st));
+  }
+  SRS_TRY(event_poll(W->ev_ragged));
+  const ListCounters c = *W->h_ctr;
+  info[4] = 1;
+  info[1] = (int64_t)c.n_local;
+  info[2] = (int64_t)c.n_local2;
+  info[3] = (int64_t)c.n_big;
+  info[0] = nseg - (int64_t)c.n_listed - (int64_t)c.n_empty - (int64_t)c.n_bad;
+  if (c.n_bad > 0)
+    return fail(SRS_ERR_INVALID_ARG,
+                "sort ragged: " + std::to_string(c.n_bad) +
+                    " segment(s) with offsets that decrease or leave [0, num] (skipped; the "
+                    "outputs are unspecified)");
+  if (c.n_listed == 0) return SRS_OK;
+
+  // ---- the listed segments: the sort's levels and LDS chain -----------------
+  // Without indices they sort IN -> OUT; with indices the prepare pass moves
+  // them to the outputs with their iota, and they sort in place there.
+  Request Q = R;
+  if (with_idx) {
+    for (int c2 = 0; c2 < Q.ncols; c2++) Q.in_cols[c2] = Q.out_cols[c2];
+    Q.in_cols[Q.ncols] = Q.out_cols[Q.ncols] = idx_out;
+    Q.widths[Q.ncols++] = 8;
+  }
+  std::vector<size_t> tmp_off;
+  const size_t tmp_bytes = col_offsets(num, Q.ncols, Q.widths, &tmp_off);
+  char* tmp = nullptr;
+  if (c.n_big > 0) {  // the levels scatter through TMP; the LDS chain touches IN and OUT only
+    SRS_TRY(ensure(W->tmp, tmp_bytes, ws_alloc_mode(), true));
+    tmp = (char*)W->tmp.p;
+  }
+  set_columns(Q, d, tmp, nullptr, false, 0, tmp_off.data(), with_idx);
+  d.stamp_acc = g_stamp_acc;
+  d.lb_status = g_lb_status;
+  d.lb_err = g_lb_err;
+  SRS_TRY(ensure(W->desc, sizeof(SortDesc)));
+  SortDesc* d_desc = (SortDesc*)W->desc.p;
+  launch_set_desc(d, d_desc, st);
+  if (with_idx) {
+    TimedScope ts("ragged_prepare", (double)num, st);
+    HIP_TRY(launch_ragged_prepare(a, st));
+    info[5] = 1;
+  }
+  LevelState S{(int64_t)c.n_big, (int64_t)c.n_local, (int64_t)c.n_local2, (int64_t)c.n_copy, 0,
+               d.ncols, d.tmp2};
+  S.pair_tiles = pair_tiles_mode(d, ks, false);
+  int level = 0;
+  while (S.nbig > 0) {
+    if (++level > 80) return fail(SRS_ERR_INTERNAL, "level limit exceeded");
+    info[4] += 2;  // (totals, counters)
+    SRS_TRY(run_level(W, ks, d_desc, S, st));
+  }
+  return run_lists_tail(W, Q, d, d_desc, S.n_local, S.n_local2, S.n_copy, false, st);
+}
+
+// ---------------------------------------------------------------------------
 // host arrays (the reference's calling convention, radixSort.hpp:1780):
 // staged PCIe copies, and the split of one host array over several GPUs
 // ---------------------------------------------------------------------------
@@ -3317,6 +3460,30 @@ int srs_sort_rows_soa_device(int64_t rows, int64_t row_len, int64_t row_stride, 
   return sort_rows_device(R, rows, row_stride, indices_out, (hipStream_t)stream);
 }
 
+int srs_sort_ragged_soa_device(int64_t num, int64_t num_segments, const int64_t* offsets,
+                               int key_kind, int up, const void* keys, int32_t num_payloads,
+                               const void* const* payloads, const uint32_t* payload_sizes,
+                               void* keys_out, void* const* payloads_out, int64_t* indices_out,
+                               void* stream) {
+  Request R;
+  SRS_TRY(build_soa(R, num, key_kind, up, 0, (void*)keys, num_payloads, (void* const*)payloads,
+                    payload_sizes, keys_out, payloads_out));
+  const bool work = num > 0 && num_segments > 0;
+  const char* shape = num_segments > (INT64_MAX >> 4) ? "num_segments + 1 overflows" : nullptr;
+  SRS_TRY(validate_outputs(R, "sort ragged", keys_out, indices_out, work ? num : 0,
+                           work ? num : 0, true, shape));
+  if (!work) return SRS_OK;
+  if (!offsets) return fail(SRS_ERR_INVALID_ARG, "offsets is NULL");
+  if ((uintptr_t)offsets % 8 != 0) return fail(SRS_ERR_INVALID_ARG, "offsets must be 8-byte aligned");
+  const size_t off_bytes = ((size_t)num_segments + 1) * sizeof(int64_t);
+  for (int o = 0; o <= R.ncols; o++) {
+    const void* op = o < R.ncols ? R.out_cols[o] : (const void*)indices_out;
+    if (op && ranges_overlap(op, (size_t)num * (o < R.ncols ? R.widths[o] : 8), offsets, off_bytes))
+      return fail(SRS_ERR_INVALID_ARG, "sort ragged outputs must not overlap the offsets");
+  }
+  return sort_ragged_device(R, num_segments, offsets, indices_out, (hipStream_t)stream);
+}
+
 int srs_topk_aos_device(int64_t num, int64_t k, int key_kind, int up, const void* elements,
                         uint32_t elem_size, void* elements_out, int64_t* indices_out,
                         void* stream) {
@@ -3683,6 +3850,22 @@ int srs_debug_last_sort_rows(int64_t* info) {
   WsLock lk;
   SRS_TRY(acquire_ws(&W, &lk));
   for (int i = 0; i < 4; i++) info[i] = W->sort_rows_info[i];
+  return SRS_OK;
+}
+
+int srs_debug_set_sort_ragged_short_max(int32_t len) {
+  if (len < -1 || len > kRowsWaveMax)
+    return fail(SRS_ERR_INVALID_ARG, "short_max must be -1 (default) or 0 .. 256");
+  g_sort_ragged_short_max.store(len);
+  return SRS_OK;
+}
+
+int srs_debug_last_sort_ragged(int64_t* info) {
+  if (!info) return fail(SRS_ERR_INVALID_ARG, "info is NULL");
+  Workspace* W = nullptr;
+  WsLock lk;
+  SRS_TRY(acquire_ws(&W, &lk));
+  for (int i = 0; i < 6; i++) info[i] = W->sort_ragged_info[i];
   return SRS_OK;
 }
 

@@ -140,6 +140,11 @@ struct ListCounters {
   unsigned long long n_fallback2; // segments handed on to the LSD local kernel
   unsigned long long n_redo;      // small-class segments the direct kernel handed to the fast one
   unsigned long long n_redo2;     // large-class segments the direct kernel handed to the fast one
+  // ragged sort (ragged_segs_kernel): segments of the caller's
+  // offsets with a bad bound (skipped), empty ones, and those offered to the lists
+  unsigned long long n_bad;
+  unsigned long long n_empty;
+  unsigned long long n_listed;
 };
 
 // Tuning constants (see DESIGN.md §4 for how they were chosen).

@@ -220,4 +220,39 @@ struct RowsPrepareArgs {
 };
 hipError_t launch_rows_prepare(const RowsPrepareArgs& a, hipStream_t st);
 
+// ---- ragged sort --------------------------------------------
+// Segment i of nseg is records [offsets[i], offsets[i + 1]) of every column
+// (dense, num records; col[0] the key column); offsets is a device array the
+// kernels read. A segment is VALID when 0 <= offsets[i] <= offsets[i + 1] <=
+// num; every kernel below tests that itself and touches no record of a
+// segment that is not, so no column is accessed outside [0, num) whatever
+// the offsets hold. SHORT segments (1 .. short_max records) belong to the
+// short kernel, LISTED ones (more than short_max) to the work lists.
+struct RaggedArgs {
+  int64_t num, nseg;
+  const int64_t* offsets;
+  int32_t ncols;
+  int32_t key_bits;
+  uint64_t mpos, mneg;  // SortDesc's key transform
+  int32_t short_max;    // 0 .. kRowsWaveMax (0: every segment of >= 1 record is listed)
+  int64_t* idx_out;     // or null
+  TopkRowsCol col[SRS_MAX_COLS];
+};
+// One wave per segment: every short segment sorted from col[].in to col[].out
+// (and its in-segment positions to idx_out). a.short_max >= 1.
+hipError_t launch_ragged_short(int key_size, const RaggedArgs& a, hipStream_t st);
+// One thread per segment: listed segments go through emit_child as
+// Seg{start, len, rbits, buf}; *ctr (zeroed by the caller) also counts the
+// bad, the empty and the listed segments. At most `cap` segments are listed
+// (valid offsets list at most num / (short_max + 1)); any further one counts
+// as bad, so the lists need `cap` entries each.
+hipError_t launch_ragged_segs(const int64_t* offsets, int64_t nseg, int64_t num, int short_max,
+                              int rbits, int buf, int64_t cap, Seg* big, Seg* local, Seg* local2,
+                              Seg* copy, ListCounters* ctr, hipStream_t st);
+// The listed segments' records copied from col[].in to col[].out and their
+// in-segment positions written to idx_out, element-parallel over [0, num);
+// no position of a short, empty or bad segment, or outside the segments, is
+// written.
+hipError_t launch_ragged_prepare(const RaggedArgs& a, hipStream_t st);
+
 }  // namespace srs

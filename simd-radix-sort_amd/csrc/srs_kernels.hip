@@ -5646,4 +5646,195 @@ hipError_t launch_rows_prepare(const RowsPrepareArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// ragged sort (srs_sort_ragged_soa_device): segments given by a
+// device array of offsets. Three plain kernels in stream order; each reads
+// the two offsets of a segment itself and skips the segment unless
+// 0 <= start <= end <= num, so garbage offsets reach no address outside the
+// columns. No workgroup reads what another wrote in the same launch (the
+// list atomics of emit_child apart).
+// ---------------------------------------------------------------------------
+constexpr int kRaggedShortThreads = 256;
+constexpr int kRaggedSegsThreads = 256;
+constexpr int kRaggedPrepThreads = 256;
+constexpr int kRaggedPrepItems = 4;
+
+// Segment s of the offsets: its start and length when the bounds are valid.
+__device__ __forceinline__ bool ragged_bounds(const int64_t* __restrict__ offsets, int64_t s,
+                                              int64_t num, int64_t* start, int64_t* len) {
+  const int64_t a = offsets[s], b = offsets[s + 1];
+  *start = a;
+  *len = (int64_t)((uint64_t)b - (uint64_t)a);  // (meaningful when valid; wraps otherwise)
+  return a >= 0 && a <= b && b <= num;
+}
+
+// rows_write for a segment of n records at `at` of the input and of the
+// output columns: record j of the result is input record si[j] of the segment.
+template <typename KT>
+__device__ __forceinline__ void ragged_write(const RaggedArgs& A, int64_t at, uint32_t n,
+                                             const uint32_t* si, uint32_t lane) {
+  constexpr int KS = (int)sizeof(KT);
+  for (uint32_t j = lane; j < n; j += 64) {
+    const uint32_t e = si[j];
+    if (e >= n) continue;  // (a padding slot: never inside the first n)
+    stw<KS>(A.col[0].out + (at + j) * KS, (uint64_t)gld<KT>(A.col[0].in + (at + e) * KS));
+    if (A.idx_out) gst<int64_t>(A.idx_out + at + j, (int64_t)e);
+  }
+  for (int c = 1; c < A.ncols; c++) {
+    const TopkRowsCol& C = A.col[c];
+    with_width(C.width, [&](auto W_) {
+      constexpr int W = decltype(W_)::value;
+      for (uint32_t j = lane; j < n; j += 64) {
+        const uint32_t e = si[j];
+        if (e < n) stw<W>(C.out + (at + j) * W, ldw<W>(C.in + (at + e) * W));
+      }
+    });
+  }
+}
+
+// One WAVE per segment, four segments to a workgroup, no workgroup barrier:
+// wave w of the grid takes segment w, and leaves at once unless the segment
+// is valid and short (1 .. short_max records). The segment is sorted whole in
+// the wave's LDS slab of kRowsWaveMax (key, position) pairs, over p2 = the
+// power of two >= its length (per wave: no wave waits for another), and every
+// column is written by sorted position, straight from the caller's input to
+// the outputs.
+template <typename KT, typename U>
+__global__ __launch_bounds__(kRaggedShortThreads) void ragged_short_kernel(const RaggedArgs A) {
+  constexpr int KS = (int)sizeof(KT);
+  constexpr int WPB = kRaggedShortThreads / 64;
+  __shared__ U ragged_sk[WPB * kRowsWaveMax];
+  __shared__ uint32_t ragged_si[WPB * kRowsWaveMax];
+  const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
+  const int64_t s = (int64_t)blockIdx.x * WPB + wave;
+  if (s >= A.nseg) return;  // (whole waves: nothing below waits for another wave)
+  int64_t at, len;
+  if (!ragged_bounds(A.offsets, s, A.num, &at, &len)) return;
+  if (len < 1 || len > A.short_max || len > kRowsWaveMax) return;
+  const uint32_t n = (uint32_t)len;
+  uint32_t p2 = 2;
+  while (p2 < n) p2 <<= 1;
+  U* const sk = ragged_sk + wave * kRowsWaveMax;
+  uint32_t* const si = ragged_si + wave * kRowsWaveMax;
+  SelectArgs a;
+  a.key_bits = A.key_bits;
+  a.mpos = A.mpos;
+  a.mneg = A.mneg;
+  const Xform<U> xf = select_xform<U>(a);
+  const char* keys = A.col[0].in + at * KS;
+  for (uint32_t e = lane; e < p2; e += 64) {
+    const bool ok = e < n;
+    sk[e] = ok ? xf((U)gld<KT>(keys + (int64_t)e * KS)) : (U)~(U)0;
+    si[e] = ok ? e : 0xffffffffu;
+  }
+  wave_lds_sync();
+  rows_bitonic(sk, si, p2, lane, 64u, [] { wave_lds_sync(); });
+  ragged_write<KT>(A, at, n, si, lane);
+}
+
+// One thread per segment: the listed segments (valid, longer than short_max)
+// through emit_child, the bad and the empty ones counted (one atomic per wave
+// and counter). A segment past the lists' capacity can only come from
+// offsets that are not non-decreasing: it is counted as bad and not listed.
+__global__ __launch_bounds__(kRaggedSegsThreads) void ragged_segs_kernel(
+    const int64_t* __restrict__ offsets, int64_t nseg, int64_t num, int32_t short_max,
+    int32_t rbits, int32_t buf, unsigned long long cap, Lists L) {
+  const int64_t s = (int64_t)blockIdx.x * kRaggedSegsThreads + threadIdx.x;
+  int64_t at = 0, len = 0;
+  bool bad = false, empty = false, list = false;
+  if (s < nseg) {
+    bad = !ragged_bounds(offsets, s, num, &at, &len);
+    empty = !bad && len == 0;
+    list = !bad && len > short_max;
+  }
+  if (list && atomicAdd(&L.ctr->n_listed, 1ull) >= cap) {
+    list = false;
+    bad = true;
+  }
+  const uint64_t mb = __ballot(bad), me = __ballot(empty);
+  if (lane_id() == 0) {
+    if (mb) atomicAdd(&L.ctr->n_bad, (unsigned long long)__popcll(mb));
+    if (me) atomicAdd(&L.ctr->n_empty, (unsigned long long)__popcll(me));
+  }
+  if (list) emit_child(L, Seg{at, len, rbits, buf});
+}
+
+// The listed segments' records from the inputs to the outputs, and the iota of
+// their in-segment positions: element-parallel over [0, num), so one long
+// segment is spread over as many workgroups as it has strips. Thread t of a
+// block takes records t, t + 256, ... of the block's 1024 consecutive
+// positions; it finds its first record's segment by a search of the offsets
+// (the last s with offsets[s] <= e) and keeps it while the next records stay
+// inside. The bounds found are tested before anything is touched: a record is
+// copied only when it lies in a valid segment longer than short_max.
+__global__ __launch_bounds__(kRaggedPrepThreads) void ragged_prepare_kernel(const RaggedArgs A) {
+  const int64_t e0 = (int64_t)blockIdx.x * (kRaggedPrepThreads * kRaggedPrepItems) + threadIdx.x;
+  int64_t pos[kRaggedPrepItems];  // in-segment position, or -1: not copied
+  int64_t at = 0, len = -1;       // the segment of the previous record (len < 0: none)
+#pragma unroll
+  for (int k = 0; k < kRaggedPrepItems; k++) {
+    const int64_t e = e0 + k * kRaggedPrepThreads;
+    pos[k] = -1;
+    if (e >= A.num) continue;
+    if (len < 0 || e < at || e - at >= len) {
+      int64_t lo = 0, hi = A.nseg;
+      while (hi - lo > 1) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (A.offsets[mid] <= e) lo = mid;
+        else hi = mid;
+      }
+      if (!ragged_bounds(A.offsets, lo, A.num, &at, &len)) len = -1;
+    }
+    if (len > A.short_max && e >= at && e - at < len) pos[k] = e - at;
+  }
+  for (int c = 0; c < A.ncols; c++) {
+    const TopkRowsCol C = A.col[c];
+    with_width(C.width, [&](auto W_) {
+      constexpr int W = decltype(W_)::value;
+      uint64_t v[kRaggedPrepItems] = {};
+#pragma unroll
+      for (int k = 0; k < kRaggedPrepItems; k++)
+        if (pos[k] >= 0) v[k] = ldw<W>(C.in + (e0 + k * kRaggedPrepThreads) * W);
+#pragma unroll
+      for (int k = 0; k < kRaggedPrepItems; k++)
+        if (pos[k] >= 0) stw<W>(C.out + (e0 + k * kRaggedPrepThreads) * W, v[k]);
+    });
+  }
+  if (A.idx_out) {
+#pragma unroll
+    for (int k = 0; k < kRaggedPrepItems; k++)
+      if (pos[k] >= 0) gst<int64_t>(A.idx_out + e0 + k * kRaggedPrepThreads, pos[k]);
+  }
+}
+
+hipError_t launch_ragged_short(int key_size, const RaggedArgs& a, hipStream_t st) {
+  constexpr int64_t kWaveSegs = kRaggedShortThreads / 64;
+  const int64_t grid = (a.nseg + kWaveSegs - 1) / kWaveSegs;
+  if (grid <= 0 || grid > 0x7fffffff || a.short_max < 1 || a.short_max > kRowsWaveMax)
+    return hipErrorInvalidValue;
+#define CALL(KT, U, CZ) ragged_short_kernel<KT, U><<<(unsigned)grid, kRaggedShortThreads, 0, st>>>(a)
+  SRS_KEY_DISPATCH(key_size, CALL)
+#undef CALL
+  return hipGetLastError();
+}
+
+hipError_t launch_ragged_segs(const int64_t* offsets, int64_t nseg, int64_t num, int short_max,
+                              int rbits, int buf, int64_t cap, Seg* big, Seg* local, Seg* local2,
+                              Seg* copy, ListCounters* ctr, hipStream_t st) {
+  const int64_t grid = (nseg + kRaggedSegsThreads - 1) / kRaggedSegsThreads;
+  if (grid <= 0 || grid > 0x7fffffff || cap < 0) return hipErrorInvalidValue;
+  ragged_segs_kernel<<<(unsigned)grid, kRaggedSegsThreads, 0, st>>>(
+      offsets, nseg, num, short_max, rbits, buf, (unsigned long long)cap,
+      Lists{big, local, local2, copy, ctr});
+  return hipGetLastError();
+}
+
+hipError_t launch_ragged_prepare(const RaggedArgs& a, hipStream_t st) {
+  constexpr int64_t per = kRaggedPrepThreads * kRaggedPrepItems;
+  const int64_t grid = (a.num + per - 1) / per;
+  if (grid <= 0 || grid > 0x7fffffff) return hipErrorInvalidValue;
+  ragged_prepare_kernel<<<(unsigned)grid, kRaggedPrepThreads, 0, st>>>(a);
+  return hipGetLastError();
+}
+
 }  // namespace srs

@@ -87,6 +87,10 @@ def lib() -> ctypes.CDLL:
                                            vp, vp, vp, vp, vp]
     L.srs_debug_set_sort_rows_route.argtypes = [ctypes.c_int]
     L.srs_debug_last_sort_rows.argtypes = [ctypes.POINTER(i64)]
+    L.srs_sort_ragged_soa_device.argtypes = [i64, i64, vp, ctypes.c_int, ctypes.c_int, vp, i32, vp,
+                                             vp, vp, vp, vp, vp]
+    L.srs_debug_set_sort_ragged_short_max.argtypes = [i32]
+    L.srs_debug_last_sort_ragged.argtypes = [ctypes.POINTER(i64)]
     L.srs_fill_synthetic_device.argtypes = [i64, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
                                             vp, i32, vp, vp, vp]
     L.srs_key_histogram_device.argtypes = [i64, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp,
@@ -448,6 +452,51 @@ def sort_rows_device(keys, *payloads, up: bool = True, key_kind: int | None = No
     return out + ((idx,) if indices else ())
 
 
+def sort_ragged_device(keys, *payloads, offsets, up: bool = True, key_kind: int | None = None,
+                       indices: bool = False, out=None, stream=None):
+    """Every segment [offsets[i], offsets[i+1]) of 1-D device columns sorted in
+    one call, out of place (srs_sort_ragged_soa_device): per segment the
+    stable sort by key, equal keys in input order. `offsets` is an int64
+    DEVICE tensor of num_segments + 1 non-decreasing values within [0,
+    len(keys)] on the keys' GPU (TypeError otherwise); it is read on the
+    device, and offsets that decrease or leave the columns raise SrsError.
+    Returns (keys_out, *payloads_out[, indices]) of the inputs' shape: `out` =
+    (keys_out, *payloads_out), clear of the inputs, or new tensors, whose
+    records outside the covered range are left as allocated; indices=True adds
+    an int64 tensor of each record's position inside its segment."""
+    import torch
+    cols = (keys,) + payloads
+    _check_columns(keys, cols)
+    if not (isinstance(offsets, torch.Tensor) and offsets.dtype == torch.int64 and
+            offsets.is_cuda and offsets.device == keys.device):
+        raise TypeError("offsets must be an int64 device tensor on the keys' GPU")
+    if not (offsets.dim() == 1 and offsets.is_contiguous()):
+        raise ValueError("offsets must be 1-D and contiguous")
+    n, nseg = keys.numel(), offsets.numel() - 1
+    kind = _torch_kind(keys) if key_kind is None else int(key_kind)
+    if out is None:
+        out = tuple(torch.empty_like(c) for c in cols)
+    else:
+        out = tuple(out)
+        if len(out) != len(cols):
+            raise ValueError("out must hold keys_out followed by every payload_out")
+        _check_columns(keys, out, "out tensors")
+        for o, i in zip(out, cols):
+            if o.element_size() != i.element_size():
+                raise ValueError("every out tensor must have its input's element size")
+    idx = torch.empty(n, dtype=torch.int64, device=keys.device) if indices else None
+    if n == 0 or nseg <= 0:  # (an empty tensor has no address to pass)
+        return out + ((idx,) if indices else ())
+    with _on_device(keys):
+        _check(lib().srs_sort_ragged_soa_device(
+            n, nseg, offsets.data_ptr(), kind, int(bool(up)), keys.data_ptr(), len(payloads),
+            _ptr_array([p.data_ptr() for p in payloads]),
+            _size_array([p.element_size() for p in payloads]), out[0].data_ptr(),
+            _ptr_array([o.data_ptr() for o in out[1:]]),
+            None if idx is None else idx.data_ptr(), _stream_ptr(stream, keys.device)))
+    return out + ((idx,) if indices else ())
+
+
 def topk_combined_device(elements, key_kind: int, k: int, up: bool = True, out=None,
                          indices: bool = False, stream=None):
     """topk_device on a DataElement array (srs_topk_aos_device): `elements`
@@ -689,6 +738,22 @@ def debug_last_sort_rows():
     current device."""
     c = (ctypes.c_int64 * 4)()
     _check(lib().srs_debug_last_sort_rows(c))
+    return tuple(int(x) for x in c)
+
+
+def debug_set_sort_ragged_short_max(length: int) -> None:
+    """The longest segment sort_ragged_device leaves to its wave-per-segment
+    kernel, process-wide (srs_debug_set_sort_ragged_short_max): -1 the default
+    (256), 0 that kernel off, 1 .. 256 the maximum."""
+    _check(lib().srs_debug_set_sort_ragged_short_max(int(length)))
+
+
+def debug_last_sort_ragged():
+    """(segments left to the short kernel, small-class / large-class / big list
+    lengths as first read back, host read-backs, 1 if the prepare pass ran) of
+    the last sort_ragged_device on the current device."""
+    c = (ctypes.c_int64 * 6)()
+    _check(lib().srs_debug_last_sort_ragged(c))
     return tuple(int(x) for x in c)
 
 
