@@ -503,6 +503,14 @@ int srs_debug_set_lookback(void* status, void* err);
  * tests lower it so that the path runs at small sizes. */
 int srs_debug_set_super_scan(int64_t min_groups);
 
+/* Global levels run in this process so far (every device, every entry point
+ * that takes the general level driver): counts[0] = all of them, counts[1] =
+ * those scattered by the tile-pair kernel, counts[2] = of those, the ones
+ * that ran without the tile-offset pass (the scatter summed its offsets from
+ * the count rows; SRS_PAIR_ROW_OFFS=0 turns that off). Tests
+ * take differences around a call to prove which path a sort took. */
+int srs_debug_level_counts(int64_t* counts);
+
 /* Segments the local-level fallback kernels took in the last sort on the
  * current device: counts[0] = handed to the stable kernel, counts[1] = handed
  * on to the LSD kernel. Synchronizes the device. Tests use it to prove that

@@ -58,6 +58,10 @@ thread_local std::string g_err = "no error";
 unsigned long long* g_stamp_acc = nullptr;  // srs_debug_set_stamp_buffer
 uint32_t* g_lb_status = nullptr;             // srs_debug_set_lookback
 unsigned long long* g_lb_err = nullptr;
+// global levels run_level has run in this process: all, those on the
+// tile-pair scatter, and of those the ones without tile_offs_kernel
+// (srs_debug_level_counts)
+std::atomic<int64_t> g_level_counts[3];
 
 // ---------------------------------------------------------------------------
 // environment knobs: the three parses, then every knob of the driver. The
@@ -117,6 +121,9 @@ SRS_KNOB_ONCE(int64_t, mid_level_max_n, mid_level_max_knob())
 bool placement_enabled() { return knob_on("SRS_PLACE"); }
 // SRS_PAIR_TILES (A/B runs of the tile-pair scatter, pair_tiles_mode)
 int pair_tiles_knob() { return (int)knob_int("SRS_PAIR_TILES", 2); }
+// SRS_PAIR_ROW_OFFS=0 (A/B runs): the tile-pair levels of a sort keep
+// tile_offs_kernel and its u32 offset rows (run_level)
+bool pair_row_offs_knob() { return knob_on("SRS_PAIR_ROW_OFFS"); }
 // SRS_XCD_ROT (placement diagnostics)
 int xcd_rotation_knob() { return (int)knob_int("SRS_XCD_ROT", 0); }
 // SRS_TABLE (A/B runs: "1" or "3" forces the digit table's kind, plan_table)
@@ -948,6 +955,7 @@ struct LevelState {
   int tmp2;                // SortDesc::tmp2
   int64_t known_len = -1;  // the length of the single big segment, when the host knows it
   int pair_tiles = 0;      // the scatter takes two count tiles per workgroup (pair_tiles_mode)
+  bool row_offs = false;   // and sums its tile offsets from the count rows (pair_row_offs_knob)
   int level = 0;           // global levels run so far (per-level timing names)
 };
 
@@ -1045,7 +1053,20 @@ int run_level(Workspace* W, int ks, const SortDesc* d_desc, LevelState& S, hipSt
   // u16 tile counts; u32 tile offsets when every segment of the level is
   // < 2^32 keys (all of them are when the level is), else u64
   const bool offs32 = level_keys < (1ull << 32);
-  SRS_TRY(ensure(W->offs, (size_t)ntiles * kMaxBins * (offs32 ? 4 : 8)));
+  const bool pairs = (S.pair_tiles & 1) && (lut == 0 || ((S.pair_tiles & 2) && lut == 2)) &&
+                     !((S.pair_tiles & 4) && lv == 1);
+  // The tile-pair scatter sums its tiles' offsets from the count rows
+  // itself (scatter_pair_tiles): such a level has no tile
+  // offset rows and does not run tile_offs_kernel.
+#ifdef SRS_DIAG_LOOKBACK
+  const bool row_offs = false;  // (the look-back is checked against the rows)
+#else
+  const bool row_offs = pairs && offs32 && S.row_offs;
+#endif
+  g_level_counts[0]++;
+  g_level_counts[1] += pairs;
+  g_level_counts[2] += row_offs;
+  if (!row_offs) SRS_TRY(ensure(W->offs, (size_t)ntiles * kMaxBins * (offs32 ? 4 : 8)));
   // (+ the super-group rows of a one-segment level's scan, launch_offsets)
   const int64_t grows = ngroups + super_rows(ngroups);
   SRS_TRY(ensure(W->gsum, (size_t)grows * kMaxBins * 4));
@@ -1075,15 +1096,17 @@ int run_level(Workspace* W, int ks, const SortDesc* d_desc, LevelState& S, hipSt
                    offs32 ? nullptr : (uint64_t*)W->offs.p, offs32 ? (uint32_t*)W->offs.p : nullptr,
                    var, (Seg*)W->big[nxt].p, (Seg*)W->local.p,
                    (Seg*)W->local2.p, (Seg*)W->copy.p, d_ctr, lut_rbits, st, (int)M.stripe,
-                   (uint32_t*)W->prun.p);
+                   (uint32_t*)W->prun.p, !row_offs);
   }
   if (g_lb_status)  // (diagnostic look-back: fresh status words per level)
     HIP_TRY(hipMemsetAsync(g_lb_status, 0, (size_t)ntiles * kMaxBins * 4, st));
   {
     TimedScope ts("scatter", (double)0, st, lv);
-    const bool pairs = (S.pair_tiles & 1) && (lut == 0 || ((S.pair_tiles & 2) && lut == 2)) &&
-                       !((S.pair_tiles & 4) && lv == 1);
-    if (pairs)
+    if (row_offs)
+      launch_scatter_pairs(ks, d_desc, plan, tile_seg, nullptr, nullptr, ntiles, lut, st, M.gt,
+                           (const uint16_t*)W->hist.p, (const uint64_t*)W->gofs.p,
+                           (const uint64_t*)W->sbase.p);
+    else if (pairs)
       launch_scatter_pairs(ks, d_desc, plan, tile_seg, (uint64_t*)W->offs.p,
                            offs32 ? (const uint32_t*)W->offs.p : nullptr, ntiles, lut, st, M.gt);
     else
@@ -1775,6 +1798,7 @@ int run_sort(Workspace* W, const Request& R, hipStream_t st) {
   SRS_TRY(start_lists(X, L, S, &done));
   if (done) return SRS_OK;
   S.pair_tiles = pair_tiles_mode(d, ks, L.aos_cols);
+  S.row_offs = pair_row_offs_knob();
 
   // ---- the levels: stripe pair or table level, then general levels ------------
   bool stripes = false;
@@ -2512,6 +2536,7 @@ int sort_rows_lists(Workspace* W, const Request& Q, int64_t rows, int64_t row_le
   LevelState S{cls == 2 ? rows : 0, cls == 0 ? rows : 0, cls == 1 ? rows : 0, 0, 0, d.ncols,
                d.tmp2};
   S.pair_tiles = pair_tiles_mode(d, ks, false);
+  S.row_offs = pair_row_offs_knob();
   if (S.nbig == 1) S.known_len = row_len;
   int level = 0;
   while (S.nbig > 0) {
@@ -2713,6 +2738,7 @@ int sort_ragged_device(const Request& R, int64_t nseg, const int64_t* offsets, i
   LevelState S{(int64_t)c.n_big, (int64_t)c.n_local, (int64_t)c.n_local2, (int64_t)c.n_copy, 0,
                d.ncols, d.tmp2};
   S.pair_tiles = pair_tiles_mode(d, ks, false);
+  S.row_offs = pair_row_offs_knob();
   int level = 0;
   while (S.nbig > 0) {
     if (++level > 80) return fail(SRS_ERR_INTERNAL, "level limit exceeded");
@@ -3664,6 +3690,12 @@ int srs_debug_last_local_classes(int64_t* counts) {
   counts[1] = (int64_t)c.n_local2;
   counts[2] = (int64_t)c.n_redo;
   counts[3] = (int64_t)c.n_redo2;
+  return SRS_OK;
+}
+
+int srs_debug_level_counts(int64_t* counts) {
+  if (!counts) return fail(SRS_ERR_INVALID_ARG, "counts is NULL");
+  for (int i = 0; i < 3; i++) counts[i] = g_level_counts[i].load();
   return SRS_OK;
 }
 

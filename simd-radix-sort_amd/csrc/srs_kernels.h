@@ -39,16 +39,21 @@ void launch_offsets(SegPlan* plan, int64_t nbig, const int32_t* group_seg, int64
                     uint64_t* offs, uint32_t* offs32, const unsigned long long* var_or,
                     Seg* big_next, Seg* local, Seg* local2, Seg* copy, ListCounters* ctr,
                     const int32_t* lut_rbits, hipStream_t st, int mode = 0,
-                    uint32_t* prun = nullptr);
+                    uint32_t* prun = nullptr, bool tile_rows = true);  // false: no tile_offs_kernel
 void launch_scatter(int key_size, const SortDesc* d, const SegPlan* plan,
                     const int32_t* tile_seg, const uint64_t* offs, const uint32_t* offs32,
                     int64_t ntiles, int lut, int ncols, hipStream_t st,
                     const GTile* gt = nullptr);
 // the same level's scatter with two count tiles per workgroup (lut 0 or 2;
-// 4- or 8-byte keys; the key plus one column or C2's pair word; no canon zero)
+// 4- or 8-byte keys; the key plus one column or C2's pair word; no canon zero).
+// row_hist != nullptr: a level without tile offset rows (launch_offsets'
+// tile_rows off, segments < 2^32 keys): every workgroup sums its tiles'
+// offsets from the count rows, the group offsets and the bucket bases
 void launch_scatter_pairs(int key_size, const SortDesc* d, const SegPlan* plan,
                           const int32_t* tile_seg, const uint64_t* offs, const uint32_t* offs32,
-                          int64_t ntiles, int lut, hipStream_t st, const GTile* gt = nullptr);
+                          int64_t ntiles, int lut, hipStream_t st, const GTile* gt = nullptr,
+                          const uint16_t* row_hist = nullptr, const uint64_t* row_gofs = nullptr,
+                          const uint64_t* row_sbase = nullptr);
 // stripe first level -> the second level's segment list (W->big, n_big),
 // tile counts (nt_over) and gathered tile table (gt); see GTile
 void launch_stripe_tables(const uint32_t* prun, int64_t nstripes, int nb, uint32_t* ptile,

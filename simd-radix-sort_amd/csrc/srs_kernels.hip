@@ -1798,18 +1798,28 @@ __device__ __forceinline__ void load_strip_t(T (&dst)[IT], const char* src, uint
   for (int k = 0; k < IT; k++) dst[k] = (T)tmp[k];
 }
 
-template <typename KT, typename U, int LUT>
+// The offsets of tile ta come from `offs` / `offs32` (tile_offs_kernel's
+// rows), or, with ROW, from what that kernel reads (PairRows): the tile's
+// own prefix over the count rows of its scan group.
+struct PairRows {
+  const uint16_t* hist;   // the level's count rows
+  const uint64_t* gofs;   // group offsets inside the segment (seg_scan_kernel / super_apply_kernel)
+  const uint64_t* sbase;  // bucket bases of the segments
+};
+
+template <typename KT, typename U, int LUT, bool ROW>
 __device__ __forceinline__ void scatter_pair_tiles(
     const SortDesc* __restrict__ desc, const SegPlan* __restrict__ plan, PairLds& L,
     const int32_t* __restrict__ tile_seg, const uint64_t* __restrict__ offs,
-    const uint32_t* __restrict__ offs32, const GTile* __restrict__ gt, int64_t ta, int64_t tb,
-    const DigitLut& lut) {
+    const uint32_t* __restrict__ offs32, const PairRows& R, const GTile* __restrict__ gt,
+    int64_t ta, int64_t tb, const DigitLut& lut) {
   constexpr int NT = kPairThreads;
   constexpr int IT = kPairItems;
   constexpr int NW = NT / 64;
   constexpr int KW = sizeof(KT) >= 8 ? 8 : 4;  // (key register width)
   typedef typename std::conditional<KW == 8, uint64_t, uint32_t>::type KR;
-  const SegPlan P = plan[tile_seg[ta]];
+  const int32_t seg = tile_seg[ta];
+  const SegPlan P = plan[seg];
   int64_t base[2] = {0, 0};
   int cnt[2] = {0, 0};
   for (int h = 0; h < 2; h++) {
@@ -1835,6 +1845,38 @@ __device__ __forceinline__ void scatter_pair_tiles(
   const int ncols = desc->ncols;
   const bool pair = desc->pair != 0;
   const bool pair_src = pair && (P.buf == BUF_TMP || P.buf == BUF_TMP2);
+  const uint32_t nb = 1u << P.bits;
+
+  // ROW: the count rows of the tiles before ta in its scan group
+  // (tile_offs_kernel's t0: at most kScanGroup - 1 rows of 1 KB, shared with
+  // the workgroups next to this one on its XCD), and the group's base. One
+  // 16-byte load per lane covers a row, so wave w takes rows w, w + NW, ...:
+  // four loads per thread. They are issued in front of the records' loads
+  // and summed behind them: loads return in issue order, so the rows are
+  // back while the records are still in flight. Rows from ta on are out of
+  // the buffer's range: they read 0 and fetch nothing.
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  constexpr int NRW = (kScanGroup - 1 + NW - 1) / NW;  // rows per wave
+  u32x4 row[ROW ? NRW : 1];
+  uint32_t gb0 = 0, gb1 = 0;  // the segment's bucket base, the group's offset in the bucket
+  if constexpr (ROW) {
+    static_assert(kMaxBins * 2 == 64 * 16, "a count row is one 16-byte load per lane");
+    const int64_t tg = (ta - P.tile_base) / kScanGroup;  // the tile's group in its segment
+    const int64_t t0 = P.tile_base + tg * kScanGroup;
+    const __amdgpu_buffer_rsrc_t rr = strip_rsrc((const char*)(R.hist + t0 * kMaxBins),
+                                                 (uint32_t)(ta - t0) * (kMaxBins * 2u));
+#pragma unroll
+    for (int j = 0; j < NRW; j++) {
+      const auto x = __builtin_amdgcn_raw_buffer_load_b128(
+          rr, (wave + (uint32_t)(j * NW)) * (kMaxBins * 2u) + (uint32_t)lane_id() * 16u, 0, 0);
+      row[j] = u32x4{x[0], x[1], x[2], x[3]};
+    }
+    // (every offset of the level fits 32 bits: the low words. No guard and
+    // no add here: either would wait for the loads in front of the records'.
+    // The rows are kMaxBins wide; bins from nb on are not used.)
+    gb0 = ((const uint32_t*)R.sbase)[2 * ((int64_t)seg * kMaxBins + threadIdx.x)];
+    gb1 = ((const uint32_t*)R.gofs)[2 * ((P.group_base + tg) * kMaxBins + threadIdx.x)];
+  }
 
   // loads: the key column, then the payload column (or the pair word)
   KR v0[IT];
@@ -1852,10 +1894,23 @@ __device__ __forceinline__ void scatter_pair_tiles(
     for (int k = 0; k < IT; k++) v1[k] = (v1[k] & 0xFFFFFFFFull) | ((uint64_t)v2[k] << 32);
   }
   int64_t my_off = 0;
-  const uint32_t nb = 1u << P.bits;
-  if (threadIdx.x < nb)
+  if constexpr (ROW) {
+    // the wave's sums of its rows (bins 8 lane .. 8 lane + 7) go to the slot
+    // area, which nothing uses before the tile scan; the bins' threads add
+    // the waves' rows there
+    u32x4 lo = {0, 0, 0, 0}, hi = {0, 0, 0, 0};  // even / odd bins (< kScanGroup x kTile)
+#pragma unroll
+    for (int j = 0; j < NRW; j++) {
+      lo += row[j] & 0xFFFFu;
+      hi += row[j] >> 16;
+    }
+    u32x4* part = (u32x4*)((uint32_t*)L.sval + wave * kMaxBins + lane_id() * 8u);
+    part[0] = u32x4{lo[0], hi[0], lo[1], hi[1]};
+    part[1] = u32x4{lo[2], hi[2], lo[3], hi[3]};
+  } else if (threadIdx.x < nb) {
     my_off = offs32 ? (int64_t)offs32[ta * kMaxBins + threadIdx.x]
                     : (int64_t)offs[ta * kMaxBins + threadIdx.x];
+  }
 
   const uint32_t mask = nb - 1;
   Xform<U, false> xf;
@@ -1882,6 +1937,12 @@ __device__ __forceinline__ void scatter_pair_tiles(
         const uint32_t c = L.wc[w][my_bin];
         L.wc[w][my_bin] = (uint16_t)tsum;
         tsum += c;
+      }
+      if constexpr (ROW) {  // the tiles before ta in its group: the waves' row sums
+        uint32_t before = 0;
+#pragma unroll
+        for (int w = 0; w < NW; w++) before += ((const uint32_t*)L.sval)[w * kMaxBins + my_bin];
+        my_off = (int64_t)(gb0 + gb1 + before);
       }
     }
     const uint32_t ex = block_excl_scan_1b<NT>(tsum, L.scan_sh);
@@ -1949,12 +2010,14 @@ __device__ __forceinline__ void scatter_pair_tiles(
 }
 
 // One pair of count tiles (2w, 2w + 1) per workgroup, XCD-aware order; a
-// pair that straddles two segments is scattered as two single tiles.
-template <typename KT, typename U, int LUT>
+// pair that straddles two segments is scattered as two single tiles. ROW:
+// no tile offset rows, every tile sums its own from the count rows (R).
+template <typename KT, typename U, int LUT, bool ROW>
 __global__ __launch_bounds__(kPairThreads, 4) void scatter_pair_kernel(
     const SortDesc* __restrict__ desc, const SegPlan* __restrict__ plan,
     const int32_t* __restrict__ tile_seg, const uint64_t* __restrict__ offs,
-    const uint32_t* __restrict__ offs32, const GTile* __restrict__ gt, int64_t ntiles) {
+    const uint32_t* __restrict__ offs32, const PairRows R, const GTile* __restrict__ gt,
+    int64_t ntiles) {
   __shared__ PairLds L;
   __shared__ alignas(16) uint16_t slut[kLutLdsEntries<LUT>];
   const int64_t ta = 2 * xcd_remap(blockIdx.x, gridDim.x);
@@ -1962,12 +2025,12 @@ __global__ __launch_bounds__(kPairThreads, 4) void scatter_pair_kernel(
   const DigitLut lut = stage_lut<LUT, kPairThreads>(desc, slut);
   if (LUT) lds_barrier();  // publishes the staged digit table
   if (tb < ntiles && tile_seg[tb] == tile_seg[ta]) {
-    scatter_pair_tiles<KT, U, LUT>(desc, plan, L, tile_seg, offs, offs32, gt, ta, tb, lut);
+    scatter_pair_tiles<KT, U, LUT, ROW>(desc, plan, L, tile_seg, offs, offs32, R, gt, ta, tb, lut);
   } else {
-    scatter_pair_tiles<KT, U, LUT>(desc, plan, L, tile_seg, offs, offs32, gt, ta, -1, lut);
+    scatter_pair_tiles<KT, U, LUT, ROW>(desc, plan, L, tile_seg, offs, offs32, R, gt, ta, -1, lut);
     if (tb < ntiles) {
       lds_barrier();  // (the first tile's slots have all been read)
-      scatter_pair_tiles<KT, U, LUT>(desc, plan, L, tile_seg, offs, offs32, gt, tb, -1, lut);
+      scatter_pair_tiles<KT, U, LUT, ROW>(desc, plan, L, tile_seg, offs, offs32, R, gt, tb, -1, lut);
     }
   }
 }
@@ -4416,7 +4479,8 @@ void launch_offsets(SegPlan* plan, int64_t nbig, const int32_t* group_seg, int64
                     uint64_t* offs, uint32_t* offs32, const unsigned long long* var_or,
                     Seg* big_next,
                     Seg* local, Seg* local2, Seg* copy, ListCounters* ctr,
-                    const int32_t* lut_rbits, hipStream_t st, int mode, uint32_t* prun) {
+                    const int32_t* lut_rbits, hipStream_t st, int mode, uint32_t* prun,
+                    bool tile_rows) {
   group_sum_kernel<<<(unsigned)ngroups, kMaxBins, 0, st>>>(plan, group_seg, hist, gsum);
   if (nbig == 1 && mode != 1 && ngroups >= g_super_min_groups && super_scan_enabled()) {
     // (the super rows live behind the group rows: the caller sizes gsum and
@@ -4433,8 +4497,10 @@ void launch_offsets(SegPlan* plan, int64_t nbig, const int32_t* group_seg, int64
                                                         big_next, local, local2, copy, ctr,
                                                         lut_rbits, mode, prun, 0);
   }
-  tile_offs_kernel<<<(unsigned)ngroups, kMaxBins, 0, st>>>(
-      plan, group_seg, hist, gofs, sbase, offs, offs32);
+  // (a level whose tile-pair scatter sums the count rows itself needs none)
+  if (tile_rows)
+    tile_offs_kernel<<<(unsigned)ngroups, kMaxBins, 0, st>>>(
+        plan, group_seg, hist, gofs, sbase, offs, offs32);
 }
 
 void launch_scatter(int key_size, const SortDesc* d, const SegPlan* plan,
@@ -4463,17 +4529,25 @@ void launch_scatter(int key_size, const SortDesc* d, const SegPlan* plan,
 
 void launch_scatter_pairs(int key_size, const SortDesc* d, const SegPlan* plan,
                           const int32_t* tile_seg, const uint64_t* offs, const uint32_t* offs32,
-                          int64_t ntiles, int lut, hipStream_t st, const GTile* gt) {
+                          int64_t ntiles, int lut, hipStream_t st, const GTile* gt,
+                          const uint16_t* row_hist, const uint64_t* row_gofs,
+                          const uint64_t* row_sbase) {
   const unsigned grid = (unsigned)((ntiles + 1) / 2);
-#define CALL_P(KT, U, LK)                                                            \
-  scatter_pair_kernel<KT, U, LK><<<grid, kPairThreads, 0, st>>>(d, plan, tile_seg, offs, \
-                                                               offs32, gt, ntiles)
+  // (row_hist: the level has no tile offset rows, launch_offsets' tile_rows off)
+  const PairRows R{row_hist, row_gofs, row_sbase};
+#define CALL_P(KT, U, LK)                                                                  \
+  if (row_hist)                                                                            \
+    scatter_pair_kernel<KT, U, LK, true><<<grid, kPairThreads, 0, st>>>(                   \
+        d, plan, tile_seg, nullptr, nullptr, R, gt, ntiles);                               \
+  else                                                                                     \
+    scatter_pair_kernel<KT, U, LK, false><<<grid, kPairThreads, 0, st>>>(                  \
+        d, plan, tile_seg, offs, offs32, R, gt, ntiles)
   if (key_size == 4) {
-    if (lut == 2) CALL_P(uint32_t, uint32_t, 2);
-    else CALL_P(uint32_t, uint32_t, 0);
+    if (lut == 2) { CALL_P(uint32_t, uint32_t, 2); }
+    else { CALL_P(uint32_t, uint32_t, 0); }
   } else {
-    if (lut == 2) CALL_P(uint64_t, uint64_t, 2);
-    else CALL_P(uint64_t, uint64_t, 0);
+    if (lut == 2) { CALL_P(uint64_t, uint64_t, 2); }
+    else { CALL_P(uint64_t, uint64_t, 0); }
   }
 #undef CALL_P
 }

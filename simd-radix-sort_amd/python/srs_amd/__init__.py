@@ -611,6 +611,15 @@ def kernel_stats(name: str):
     return n.value, ms.value, el.value
 
 
+def level_counts():
+    """(all, tile-pair, tile-pair without the tile-offset pass): the global
+    levels run in this process so far (srs_debug_level_counts). Take the
+    difference around a call to see which path its levels took."""
+    c = (ctypes.c_int64 * 3)()
+    _check(lib().srs_debug_level_counts(c))
+    return tuple(int(x) for x in c)
+
+
 def last_fallbacks():
     """(stable, lsd): local segments the last sort on the current device
     handed to the stable / LSD fallback kernels (synchronizes the device)."""
