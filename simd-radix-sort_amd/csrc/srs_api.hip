@@ -12,17 +12,19 @@
 // Two small control read-backs per level (tile/histogram totals, list
 // counters) size the next launches. Everything else stays on the device.
 //
+// What other units call is declared, with the structs, in srs_driver.h; the
+// batched calls built on it (top-k, row-wise, ragged) are srs_batch.hip.
+//
 // Sections, in order:
 //   errors and the environment knobs (every getenv of this file)
 //   kernel timing (TimedScope, the statistics bench.py reads by name)
 //   allocation: big_alloc, placed_alloc, ensure
-//   Workspace, WsScope (lock + stream order of one call)
-//   descriptors: Request, init_desc, set_columns
+//   the workspace registry, WsUse / WsScope (lock + stream order of one call)
 //   one level: plan_balanced_level, plan_range_level (device halves; the
-//     arithmetic is srs_plan.hip), LevelSpec, run_level
+//     arithmetic is srs_plan.hip), level_state, run_level
+//   descriptors and the list driver: set_columns, list_begin, list_finish
 //   the sort: run_small, choose_layout, plan_first_level, start_lists,
 //     run_stripe_levels, run_sort, run_lists_tail, run_partition
-//   top-k, row-wise top-k, row-wise sort; validate_outputs
 //   host arrays: staging rings, host_sort_single, host_sort_split
 //   request builders and the C ABI
 #include <hip/hip_runtime.h>
@@ -43,21 +45,21 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/srs_c_api.h"
-#include "srs_common.h"
-#include "srs_kernels.h"
+#include "srs_driver.h"
 #include "srs_plan.h"
 
+// (what srs_driver.h declares is defined outside the unnamed namespace)
 namespace srs {
-namespace {
 
 static_assert(SRS_MAX_COLS >= SRS_MAX_PAYLOADS + 1, "descriptor columns: key + payloads");
 static_assert(sizeof(SortDesc) <= 4096, "SortDesc is a kernel argument (start_kernel)");
 
-thread_local std::string g_err = "no error";
 unsigned long long* g_stamp_acc = nullptr;  // srs_debug_set_stamp_buffer
 uint32_t* g_lb_status = nullptr;             // srs_debug_set_lookback
 unsigned long long* g_lb_err = nullptr;
+
+namespace {
+thread_local std::string g_err = "no error";
 // global levels run_level has run in this process: all, those on the
 // tile-pair scatter, and of those the ones without tile_offs_kernel
 // (srs_debug_level_counts)
@@ -79,11 +81,43 @@ bool knob_set(const char* name) {
   const char* e = knob_str(name);
   return e && *e && *e != '0';
 }
+}  // namespace
+
 int64_t knob_int(const char* name, int64_t dflt) {
   const char* e = knob_str(name);
   return (e && *e) ? atoll(e) : dflt;
 }
 
+int fail(int code, const std::string& msg) {
+  g_err = msg;
+  return code;
+}
+
+int key_size_of(int kind) {
+  switch (kind) {
+    case SRS_KEY_U8: case SRS_KEY_I8: return 1;
+    case SRS_KEY_U16: case SRS_KEY_I16: return 2;
+    case SRS_KEY_U32: case SRS_KEY_I32: case SRS_KEY_F32: return 4;
+    case SRS_KEY_U64: case SRS_KEY_I64: case SRS_KEY_F64: return 8;
+    default: return 0;
+  }
+}
+
+size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// Where ncols columns of n elements sit in one buffer, each aligned to 256
+// bytes; returns the buffer's size.
+size_t col_offsets(int64_t n, int ncols, const uint32_t* widths, std::vector<size_t>* off) {
+  size_t total = 0;
+  off->clear();
+  for (int c = 0; c < ncols; c++) {
+    off->push_back(total);
+    total += align_up((size_t)n * widths[c], 256);
+  }
+  return total;
+}
+
+namespace {
 // read once per process:
 #define SRS_KNOB_ONCE(type, fn, expr) \
   type fn() {                         \
@@ -117,17 +151,20 @@ int64_t mid_level_max_knob() {
   return std::min<int64_t>(e && *e ? (int64_t)atof(e) : kMidLevelMaxKeys, kMidLevelMaxKeys);
 }
 SRS_KNOB_ONCE(int64_t, mid_level_max_n, mid_level_max_knob())
-// read on every call: SRS_PLACE=0: plain allocations (A/B runs of placed_alloc)
-bool placement_enabled() { return knob_on("SRS_PLACE"); }
+// read on every call:
+#define SRS_KNOB(type, fn, expr) \
+  type fn() { return (expr); }
+// SRS_PLACE=0: plain allocations (A/B runs of placed_alloc)
+SRS_KNOB(bool, placement_enabled, knob_on("SRS_PLACE"))
 // SRS_PAIR_TILES (A/B runs of the tile-pair scatter, pair_tiles_mode)
-int pair_tiles_knob() { return (int)knob_int("SRS_PAIR_TILES", 2); }
+SRS_KNOB(int, pair_tiles_knob, (int)knob_int("SRS_PAIR_TILES", 2))
 // SRS_PAIR_ROW_OFFS=0 (A/B runs): the tile-pair levels of a sort keep
 // tile_offs_kernel and its u32 offset rows (run_level)
-bool pair_row_offs_knob() { return knob_on("SRS_PAIR_ROW_OFFS"); }
+SRS_KNOB(bool, pair_row_offs_knob, knob_on("SRS_PAIR_ROW_OFFS"))
 // SRS_XCD_ROT (placement diagnostics)
-int xcd_rotation_knob() { return (int)knob_int("SRS_XCD_ROT", 0); }
+SRS_KNOB(int, xcd_rotation_knob, (int)knob_int("SRS_XCD_ROT", 0))
 // SRS_TABLE (A/B runs: "1" or "3" forces the digit table's kind, plan_table)
-const char* table_knob() { return knob_str("SRS_TABLE"); }
+SRS_KNOB(const char*, table_knob, knob_str("SRS_TABLE"))
 
 // Fewest small-class segments for which the direct kernel runs. Below it the
 // fast kernel alone is cheaper: the direct kernel's hand-over list costs one
@@ -137,46 +174,11 @@ const char* table_knob() { return knob_str("SRS_TABLE"); }
 // with the direct kernel): 2^18 0.373 / 0.427, 2^22 0.068 / 0.079, 2^24
 // 0.0441 / 0.0447; at 1e9 (262144 segments) the direct kernel saves ~0.9 ms.
 // Read on every call (tests lower it to reach the kernel at small sizes).
-int64_t direct_min_segs() { return knob_int("SRS_DIRECT_MIN_SEGS", 8192); }
-
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-
-#define HIP_TRY(expr)                                                            \
-  do {                                                                           \
-    hipError_t e_ = (expr);                                                      \
-    if (e_ != hipSuccess)                                                        \
-      return fail(e_ == hipErrorOutOfMemory ? SRS_ERR_OUT_OF_MEMORY : SRS_ERR_HIP, \
-                  std::string(#expr " -> ") + hipGetErrorString(e_));            \
-  } while (0)
-
-#define SRS_TRY(expr)          \
-  do {                         \
-    int r_ = (expr);           \
-    if (r_ != SRS_OK) return r_; \
-  } while (0)
-
-int key_size_of(int kind) {
-  switch (kind) {
-    case SRS_KEY_U8: case SRS_KEY_I8: return 1;
-    case SRS_KEY_U16: case SRS_KEY_I16: return 2;
-    case SRS_KEY_U32: case SRS_KEY_I32: case SRS_KEY_F32: return 4;
-    case SRS_KEY_U64: case SRS_KEY_I64: case SRS_KEY_F64: return 8;
-    default: return 0;
-  }
-}
+SRS_KNOB(int64_t, direct_min_segs, knob_int("SRS_DIRECT_MIN_SEGS", 8192))
 
 // ---------------------------------------------------------------------------
 // kernel timing (optional; HIP events around every launch on its stream)
 // ---------------------------------------------------------------------------
-struct TimingRec {
-  std::string name;
-  std::string name2;  // optional second family (per-level names: "scatter.L1")
-  hipEvent_t a, b;
-  double elems;
-};
 struct KStat {
   int64_t launches = 0;
   double ms = 0;
@@ -205,33 +207,26 @@ hipEvent_t get_event() {
   return e;
 }
 
-struct TimedScope {
-  bool on = false;
-  TimingRec rec;
-  hipStream_t st;
-  TimedScope(const char* name, double elems, hipStream_t s, int level = 0) : st(s) {
-    std::lock_guard<std::mutex> lk(g_tmu);
-    if (!timing_wants(name)) return;
-    rec.name = name;
-    if (level > 0) rec.name2 = std::string(name) + ".L" + std::to_string(level);
-    rec.elems = elems;
-    rec.a = get_event();
-    rec.b = get_event();
-    if (!rec.a || !rec.b) return;
-    on = hipEventRecord(rec.a, st) == hipSuccess;
-  }
-  ~TimedScope() {
-    if (!on) return;
-    std::lock_guard<std::mutex> lk(g_tmu);
-    if (hipEventRecord(rec.b, st) == hipSuccess) g_pending.push_back(rec);
-  }
-};
+}  // namespace
 
-bool timing_enabled() {
+TimedScope::TimedScope(const char* name, double elems, hipStream_t s, int level) : st(s) {
   std::lock_guard<std::mutex> lk(g_tmu);
-  return g_timing != 0;
+  if (!timing_wants(name)) return;
+  rec.name = name;
+  if (level > 0) rec.name2 = std::string(name) + ".L" + std::to_string(level);
+  rec.elems = elems;
+  rec.a = get_event();
+  rec.b = get_event();
+  if (!rec.a || !rec.b) return;
+  on = hipEventRecord(rec.a, st) == hipSuccess;
+}
+TimedScope::~TimedScope() {
+  if (!on) return;
+  std::lock_guard<std::mutex> lk(g_tmu);
+  if (hipEventRecord(rec.b, st) == hipSuccess) g_pending.push_back(rec);
 }
 
+namespace {
 void note_elems(const char* name, double elems, int level = 0) {
   std::lock_guard<std::mutex> lk(g_tmu);
   if (!timing_wants(name)) return;
@@ -264,12 +259,6 @@ void drain_timing_locked() {
 // ---------------------------------------------------------------------------
 // per-device workspace (grown on demand, reused across calls)
 // ---------------------------------------------------------------------------
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  int mode = 0;  // how p was allocated (BigAlloc); 0 = hipMalloc
-};
-
 // ---- large-buffer allocation (the O(n) workspace: TMP, TMP2, staging) ------
 // SRS_WS_ALLOC selects how the big workspace buffers are backed (diagnostics
 // of the placement-dependent write rate): "malloc" (default,
@@ -291,16 +280,6 @@ struct VmmRec {
 };
 std::mutex g_vmu;
 std::map<void*, VmmRec> g_vmm;
-
-int ws_alloc_mode() {
-  const char* e = knob_str("SRS_WS_ALLOC");
-  if (!e || !*e || !strcmp(e, "malloc")) return ALLOC_MALLOC;
-  if (!strcmp(e, "contig")) return ALLOC_CONTIG;
-  if (!strcmp(e, "vmm")) return ALLOC_VMM;
-  if (!strcmp(e, "vmmshuf")) return ALLOC_VMM_SHUF;
-  if (!strcmp(e, "vmm2m")) return ALLOC_VMM_2M;
-  return ALLOC_MALLOC;
-}
 
 bool is_vmm(int mode) { return mode == ALLOC_VMM || mode == ALLOC_VMM_SHUF || mode == ALLOC_VMM_2M; }
 
@@ -521,21 +500,6 @@ hipError_t ws_free(void* p, int mode) {
   return big_free(p, mode);
 }
 
-int ensure(DevBuf& b, size_t bytes, int mode = ALLOC_MALLOC, bool placed = false) {
-  if (b.bytes >= bytes && b.p) return SRS_OK;
-  if (b.p) {
-    HIP_TRY(ws_free(b.p, b.mode));
-    b.p = nullptr;
-    b.bytes = 0;
-  }
-  size_t want = std::max<size_t>(bytes, 256);
-  if (placed) HIP_TRY(placed_alloc(&b.p, want, mode));
-  else HIP_TRY(big_alloc(&b.p, want, mode));
-  b.bytes = want;
-  b.mode = mode;
-  return SRS_OK;
-}
-
 // Growing a list that already holds live entries (copy then swap).
 int ensure_keep(DevBuf& b, size_t bytes, size_t live_bytes, hipStream_t st) {
   if (b.bytes >= bytes && b.p) return SRS_OK;
@@ -552,13 +516,64 @@ int ensure_keep(DevBuf& b, size_t bytes, size_t live_bytes, hipStream_t st) {
   return SRS_OK;
 }
 
+std::mutex g_wmu;  // the map below
+// (never destroyed: at process exit the HIP runtime -- or a profiler's tool
+// library -- may already be torn down, and ~Workspace would call into it;
+// a segfault after rocprofv3's finalisation. srs_release_workspace frees.)
+std::map<int, std::shared_ptr<Workspace>>& g_ws = *new std::map<int, std::shared_ptr<Workspace>>;
+
+int get_ws_locked(std::shared_ptr<Workspace>* out) {
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  auto it = g_ws.find(dev);
+  if (it != g_ws.end()) {
+    *out = it->second;
+    return SRS_OK;
+  }
+  auto w = std::make_shared<Workspace>();
+  HIP_TRY(hipHostMalloc((void**)&w->h_ctr, sizeof(ListCounters), hipHostMallocDefault));
+  HIP_TRY(hipHostMalloc((void**)&w->h_totals, 4 * sizeof(uint64_t), hipHostMallocDefault));
+  // (coherent: the mid-size kernel stores into it while the host polls)
+  HIP_TRY(hipHostMalloc((void**)&w->h_mid, sizeof(MidFlag), hipHostMallocCoherent));
+  memset(w->h_mid, 0, sizeof(MidFlag));
+  g_ws[dev] = w;
+  *out = w;
+  return SRS_OK;
+}
+}  // namespace
+
+int ws_alloc_mode() {
+  const char* e = knob_str("SRS_WS_ALLOC");
+  if (!e || !*e || !strcmp(e, "malloc")) return ALLOC_MALLOC;
+  if (!strcmp(e, "contig")) return ALLOC_CONTIG;
+  if (!strcmp(e, "vmm")) return ALLOC_VMM;
+  if (!strcmp(e, "vmmshuf")) return ALLOC_VMM_SHUF;
+  if (!strcmp(e, "vmm2m")) return ALLOC_VMM_2M;
+  return ALLOC_MALLOC;
+}
+
+int ensure(DevBuf& b, size_t bytes, int mode, bool placed) {
+  if (b.bytes >= bytes && b.p) return SRS_OK;
+  if (b.p) {
+    HIP_TRY(ws_free(b.p, b.mode));
+    b.p = nullptr;
+    b.bytes = 0;
+  }
+  size_t want = std::max<size_t>(bytes, 256);
+  if (placed) HIP_TRY(placed_alloc(&b.p, want, mode));
+  else HIP_TRY(big_alloc(&b.p, want, mode));
+  b.bytes = want;
+  b.mode = mode;
+  return SRS_OK;
+}
+
 // A short host wait on the sort's stream (a control read-back): polled for
 // up to 20 ms, then waited for. hipStreamSynchronize's blocking wake-up
 // costs ~30 us per call (the mid-size measurements), several
 // times per sort; a level's kernels take a few ms at most, so the poll ends
 // the wait in ~1 us.
 // a spin-wait hint (x86 `pause`; elsewhere a yield)
-inline void cpu_relax() {
+void cpu_relax() {
 #if defined(__x86_64__) || defined(__i386__)
   __builtin_ia32_pause();
 #else
@@ -583,118 +598,28 @@ int sync_poll(hipStream_t st) {
   return SRS_OK;
 }
 
-struct Workspace {
-  DevBuf tmp;         // TMP data buffer (same footprint as the input)
-  DevBuf tmp2;        // TMP2: AoS records as SoA slice columns (SortDesc::tmp2)
-  DevBuf stage;       // device copy of host arrays (host-pointer API)
-  DevBuf desc;        // SortDesc
-  DevBuf big[2], local, local2, copy, fallback, fallback2, redo, redo2;
-  DevBuf plan, tcount, gcount, tbase, gbase, var, sbase;
-  DevBuf tile_seg, group_seg, hist, offs, gsum, gofs, scan_tmp, totals, ctr;
-  DevBuf shist, lut, lut_rbits;  // balanced first level (sampled histogram, digit table)
-  // stripe first level: piece sizes and tile prefixes, bucket totals, the
-  // second level's tile counts and gathered tile table (GTile)
-  DevBuf prun, ptile, btot, bnt, btile, nt_over, gtile, gorder;
-  int64_t gorder_cap = 0;
-  DevBuf mid;  // mid-size single launch: the tiles' key OR / AND, their digit counts
-  DevBuf midbar;  // and its grid barrier's words (zeroed once)
-  // top-k: the compact columns of the selected records, the select pass's
-  // histogram row, the tally's tile counts / bases / scan temp, the gather's
-  // column descriptor; the row's pinned copy; what the last call did
-  DevBuf sel, selhist, selcnt, seldesc;
-  unsigned long long* h_sel = nullptr;
-  int64_t topk_info[3] = {0, 0, 0};
-  // row-wise top-k: the kernel's pass counter (one u64); what the last call did
-  DevBuf rowspass;
-  int64_t topk_rows_info[4] = {0, 0, 0, 0};
-  bool rows_pass_pending = false;  // info[2] is still in rowspass
-  // row-wise sort: the rows kernel's pass counter (unused, its own word so
-  // that the top-k hook's stays that call's); what the last call did
-  DevBuf sortrowspass;
-  int64_t sort_rows_info[4] = {0, 0, 0, 0};
-  // ragged sort: what the last call did; the event behind its counter copy
-  int64_t sort_ragged_info[6] = {0, 0, 0, 0, 0, 0};
-  hipEvent_t ev_ragged = nullptr;
-  hipStream_t side = nullptr;  // medium sorts: the large local class's stream
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  ListCounters* h_ctr = nullptr;
-  uint64_t* h_totals = nullptr;
-  MidFlag* h_mid = nullptr;        // the mid-size launch's early answer
-  unsigned long long mid_seq = 0;  // (its sequence numbers)
-  // Stream order of the workspace: the last call's kernels may still be
-  // queued on its stream when the call returns. `idle` is recorded on that
-  // stream at the end of every call; the next call's stream waits for it
-  // before its first workspace write (WsUse).
-  hipEvent_t idle = nullptr;
-  bool idle_pending = false;
-  // single-launch small sorts (run_small): which fallback bodies ran, for
-  // srs_debug_last_fallbacks. One slot per stream: small sorts skip the
-  // workspace's stream-order wait, so sorts on different streams must not
-  // share a slot (the map is only touched under `mu`).
-  std::map<hipStream_t, DevBuf> small_taken;
-  bool last_small = false;
-  hipStream_t last_small_stream = nullptr;
-  // one call at a time per device (calls on different devices run in
-  // parallel: the multi-GPU host split sorts its shards from several threads)
-  std::mutex mu;
-  // Freed when the last holder lets go (srs_release_workspace only drops the
-  // registry's reference, so a call that has looked the workspace up keeps
-  // it alive until it returns).
-  ~Workspace() {
-    if (idle) {  // the last call's kernels may still read the buffers
-      (void)hipEventSynchronize(idle);
-      (void)hipEventDestroy(idle);
-    }
-    DevBuf* bufs[] = {&tmp, &tmp2, &stage, &desc, &big[0], &big[1], &local, &local2, &fallback,
-                      &fallback2, &redo, &redo2, &shist, &lut, &lut_rbits, &copy, &plan, &tcount,
-                      &gcount, &tbase, &gbase, &var, &sbase, &tile_seg, &group_seg, &hist, &offs,
-                      &gsum, &gofs, &scan_tmp, &totals, &ctr, &prun, &ptile, &btot, &bnt, &btile,
-                      &nt_over, &gtile, &gorder, &mid, &midbar, &sel, &selhist, &selcnt, &seldesc,
-                      &rowspass, &sortrowspass};
-    for (DevBuf* b : bufs) free_buf(*b);
-    for (auto& t : small_taken) free_buf(t.second);
-    if (h_sel) (void)hipHostFree(h_sel);
-    if (h_ctr) (void)hipHostFree(h_ctr);
-    if (h_totals) (void)hipHostFree(h_totals);
-    if (h_mid) (void)hipHostFree(h_mid);
-    if (side) (void)hipStreamDestroy(side);
-    if (ev_fork) (void)hipEventDestroy(ev_fork);
-    if (ev_join) (void)hipEventDestroy(ev_join);
-    if (ev_ragged) (void)hipEventDestroy(ev_ragged);
-    (void)hipGetLastError();  // (release-time failures leave no sticky error behind)
+Workspace::~Workspace() {
+  if (idle) {  // the last call's kernels may still read the buffers
+    (void)hipEventSynchronize(idle);
+    (void)hipEventDestroy(idle);
   }
-};
-
-std::mutex g_wmu;  // the map below
-// (never destroyed: at process exit the HIP runtime -- or a profiler's tool
-// library -- may already be torn down, and ~Workspace would call into it;
-// a segfault after rocprofv3's finalisation. srs_release_workspace frees.)
-std::map<int, std::shared_ptr<Workspace>>& g_ws = *new std::map<int, std::shared_ptr<Workspace>>;
-
-// A workspace held for one call: the reference keeps it alive, the lock
-// (taken after the lookup, released first) makes the call its only user.
-struct WsLock {
-  std::shared_ptr<Workspace> ref;
-  std::unique_lock<std::mutex> lk;
-};
-
-int get_ws_locked(std::shared_ptr<Workspace>* out) {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  auto it = g_ws.find(dev);
-  if (it != g_ws.end()) {
-    *out = it->second;
-    return SRS_OK;
-  }
-  auto w = std::make_shared<Workspace>();
-  HIP_TRY(hipHostMalloc((void**)&w->h_ctr, sizeof(ListCounters), hipHostMallocDefault));
-  HIP_TRY(hipHostMalloc((void**)&w->h_totals, 4 * sizeof(uint64_t), hipHostMallocDefault));
-  // (coherent: the mid-size kernel stores into it while the host polls)
-  HIP_TRY(hipHostMalloc((void**)&w->h_mid, sizeof(MidFlag), hipHostMallocCoherent));
-  memset(w->h_mid, 0, sizeof(MidFlag));
-  g_ws[dev] = w;
-  *out = w;
-  return SRS_OK;
+  DevBuf* bufs[] = {&tmp, &tmp2, &stage, &desc, &big[0], &big[1], &local, &local2, &fallback,
+                    &fallback2, &redo, &redo2, &shist, &lut, &lut_rbits, &copy, &plan, &tcount,
+                    &gcount, &tbase, &gbase, &var, &sbase, &tile_seg, &group_seg, &hist, &offs,
+                    &gsum, &gofs, &scan_tmp, &totals, &ctr, &prun, &ptile, &btot, &bnt, &btile,
+                    &nt_over, &gtile, &gorder, &mid, &midbar, &sel, &selhist, &selcnt, &seldesc,
+                    &rowspass, &sortrowspass};
+  for (DevBuf* b : bufs) free_buf(*b);
+  for (auto& t : small_taken) free_buf(t.second);
+  if (h_sel) (void)hipHostFree(h_sel);
+  if (h_ctr) (void)hipHostFree(h_ctr);
+  if (h_totals) (void)hipHostFree(h_totals);
+  if (h_mid) (void)hipHostFree(h_mid);
+  if (side) (void)hipStreamDestroy(side);
+  if (ev_fork) (void)hipEventDestroy(ev_fork);
+  if (ev_join) (void)hipEventDestroy(ev_join);
+  if (ev_ragged) (void)hipEventDestroy(ev_ragged);
+  (void)hipGetLastError();  // (release-time failures leave no sticky error behind)
 }
 
 // The current device's workspace, locked for this call (lk holds a reference
@@ -711,71 +636,26 @@ int acquire_ws(Workspace** out, WsLock* lk) {
   return SRS_OK;
 }
 
-size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-// Where ncols columns of n elements sit in one buffer, each aligned to 256
-// bytes; returns the buffer's size.
-size_t col_offsets(int64_t n, int ncols, const uint32_t* widths, std::vector<size_t>* off) {
-  size_t total = 0;
-  off->clear();
-  for (int c = 0; c < ncols; c++) {
-    off->push_back(total);
-    total += align_up((size_t)n * widths[c], 256);
-  }
-  return total;
+int WsUse::begin(Workspace* w, hipStream_t s) {
+  W = w;
+  st = s;
+  if (!W->idle) HIP_TRY(hipEventCreateWithFlags(&W->idle, hipEventDisableTiming));
+  if (W->idle_pending) HIP_TRY(hipStreamWaitEvent(st, W->idle, 0));
+  return SRS_OK;
+}
+WsUse::~WsUse() {
+  if (W && W->idle) W->idle_pending = hipEventRecord(W->idle, st) == hipSuccess;
 }
 
-// Holds the workspace for one call on stream `st` (under W->mu): waits on the
-// device for the previous call's work on the workspace (any stream), and
-// marks the end of this call's work when it goes out of scope, also on error.
-struct WsUse {
-  Workspace* W = nullptr;
-  hipStream_t st = nullptr;
-  int begin(Workspace* w, hipStream_t s) {
-    W = w;
-    st = s;
-    if (!W->idle) HIP_TRY(hipEventCreateWithFlags(&W->idle, hipEventDisableTiming));
-    if (W->idle_pending) HIP_TRY(hipStreamWaitEvent(st, W->idle, 0));
-    return SRS_OK;
-  }
-  ~WsUse() {
-    if (W && W->idle) W->idle_pending = hipEventRecord(W->idle, st) == hipSuccess;
-  }
-};
+int WsScope::begin(hipStream_t st) {
+  if (!W) SRS_TRY(lock());
+  return use.begin(W, st);
+}
 
-// One call's hold on the current device's workspace: the lock, then (begin)
-// its place in the workspace's stream order. `use` goes first on scope exit.
-struct WsScope {
-  Workspace* W = nullptr;
-  WsLock lk;
-  WsUse use;
-  int lock() { return acquire_ws(&W, &lk); }
-  int begin(hipStream_t st) {
-    if (!W) SRS_TRY(lock());
-    return use.begin(W, st);
-  }
-};
-
+namespace {
 // ---------------------------------------------------------------------------
 // the sort driver (device pointers)
 // ---------------------------------------------------------------------------
-struct Request {
-  int64_t num;
-  int kind;
-  int up;
-  int64_t thresh;
-  bool aos;
-  uint32_t elem_size;                // AoS record size
-  void* in_cols[SRS_MAX_PAYLOADS + 1];
-  void* out_cols[SRS_MAX_PAYLOADS + 1];
-  uint32_t widths[SRS_MAX_PAYLOADS + 1];
-  int ncols;                         // SoA: 1 + payloads; AoS: 1
-  const int64_t* seg_bounds = nullptr;  // optional: sort [b[i], b[i+1]) independently
-  int64_t nsegs = 0;
-  int known_top_bits = 0;               // every segment's keys agree on these top bits
-  int leaf_mode = SRS_LEAF_SORTED;      // SRS_LEAF_UNSORTED: CmpSorterNoSort
-};
-
 // SortDesc::leaf_skip of a request: CmpSorterNoSort leaves every leaf of
 // <= cmpSortThreshold keys in partition order (src/cmp_sorters.hpp:66-78)
 int32_t leaf_skip_of(const Request& R) {
@@ -809,14 +689,6 @@ void key_masks(int kind, int up, SortDesc& d) {
   d.signbit = sb;
   d.negzero = sb;  // bit pattern of -0.0
   d.key_bits = kb;
-}
-
-// A zeroed descriptor with the key transform of (kind, up).
-SortDesc init_desc(int kind, int up) {
-  SortDesc d;
-  memset(&d, 0, sizeof d);
-  key_masks(kind, up, d);
-  return d;
 }
 
 // ---- balanced first level ---------------------------------------------------
@@ -923,6 +795,19 @@ int plan_balanced_level(Workspace* W, const Request& R, const SortDesc& d, hipSt
   return upload(t2.data(), t2.size() * 2, align_up(t2.size() * sizeof(uint16_t), 16));
 }
 
+int run_lists_tail(Workspace* W, const Request& R, const SortDesc& d, const SortDesc* d_desc,
+                   int64_t n_local, int64_t n_local2, int64_t n_copy, bool aos_cols,
+                   hipStream_t st);
+}  // namespace
+
+// A zeroed descriptor with the key transform of (kind, up).
+SortDesc init_desc(int kind, int up) {
+  SortDesc d;
+  memset(&d, 0, sizeof d);
+  key_masks(kind, up, d);
+  return d;
+}
+
 // The tile-pair scatter (scatter_pair_kernel): where it
 // pays, as flags: 1 on plain-digit levels, 2 also on small-digit-table
 // levels, 4 not on the first level. Measured in one process, arms
@@ -948,47 +833,24 @@ int pair_tiles_mode(const SortDesc& d, int ks, bool aos_slices) {
   return aos_slices ? (1 | 4) : ks == 4 ? (1 | 2) : 1;
 }
 
-struct LevelState {
-  int64_t nbig, n_local, n_local2, n_copy;
-  int cur;
-  int ncols;               // columns moved with the keys (SortDesc::ncols)
-  int tmp2;                // SortDesc::tmp2
-  int64_t known_len = -1;  // the length of the single big segment, when the host knows it
-  int pair_tiles = 0;      // the scatter takes two count tiles per workgroup (pair_tiles_mode)
-  bool row_offs = false;   // and sums its tile offsets from the count rows (pair_row_offs_knob)
-  int level = 0;           // global levels run so far (per-level timing names)
-};
+// The state a sort's levels start from: the lists' lengths, the single big
+// segment's length where the host knows it, and how the levels scatter (the
+// one place that decides that for a sort; run_partition sets its own).
+LevelState level_state(const SortDesc& d, int ks, bool aos_slices, int64_t nbig, int64_t n_local,
+                       int64_t n_local2, int64_t n_copy, int64_t known_len) {
+  LevelState S{nbig, n_local, n_local2, n_copy, 0, d.ncols, d.tmp2, known_len};
+  S.pair_tiles = pair_tiles_mode(d, ks, aos_slices);
+  S.row_offs = pair_row_offs_knob();
+  return S;
+}
 
 // One global MSB level over every large segment in W->big[S.cur]:
 // plan -> bases -> count -> offsets + children -> scatter. Children go to
 // W->big[S.cur ^ 1] / the local lists / the copy list; S is updated from the
 // device counters. What the level is comes in as a LevelSpec; the default
 // one is a general level: every segment's digit chosen by the plan kernel.
-enum TableKind {
-  TABLE_NONE = 0,   // a plain digit
-  TABLE_ANY = 1,    // a digit table of any kind (SortDesc::digit_lut)
-  TABLE_SMALL = 2,  // a small kind (key ranges, split table: the kernels with the small LDS table)
-};
-// How a level reads and hands on its segments: 1 a stripe level (its
-// segments are stripes of the input, partitioned each on its own; the next
-// level's segments are the buckets, read through a gathered tile table); 2
-// that gathered level. See GTile (srs_common.h).
-enum StripeMode { STRIPE_NONE = 0, STRIPE_LEVEL = 1, STRIPE_GATHERED = 2 };
-struct LevelSpec {
-  int bits = 0;                     // the digit's width; 0: the plan kernel chooses per segment
-  bool plain = false;               // bits > 0: a plain digit of that width (else the table's)
-  TableKind table = TABLE_NONE;
-  const int32_t* rbits = nullptr;   // a table level: its groups' rbits (device)
-  StripeMode stripe = STRIPE_NONE;
-  const GTile* gt = nullptr;        // gathered level
-  const int32_t* nt_over = nullptr; // gathered level: tiles per segment
-  const int32_t* torder = nullptr;  // gathered level: the count's tile order (stripe-major)
-  int key_bits = 0;                 // stripe level
-  bool home = false;                // every bucket of this level is final: scatter to OUT
-};
-
 int run_level(Workspace* W, int ks, const SortDesc* d_desc, LevelState& S, hipStream_t st,
-              const LevelSpec& M = LevelSpec()) {
+              const LevelSpec& M) {
   // (the launchers' convention: a forced plain digit as a negative width)
   const int force_bits = M.plain ? -M.bits : M.bits;
   const int lut = (int)M.table;
@@ -1159,7 +1021,7 @@ int run_level(Workspace* W, int ks, const SortDesc* d_desc, LevelState& S, hipSt
 // TMP2 the workspace (AoS records as one column, or as 8-byte slices that are
 // dense SoA columns in the workspace when aos_cols).
 void set_columns(const Request& R, SortDesc& d, char* tmp, char* tmp2, bool aos_cols,
-                 size_t slice_bytes, const size_t* tmp_off, bool inplace, bool pair = false) {
+                 size_t slice_bytes, const size_t* tmp_off, bool inplace, bool pair) {
   const int ks = key_size_of(R.kind);
   if (R.aos) {
     const uint32_t E = R.elem_size;
@@ -1206,6 +1068,59 @@ bool is_inplace(const Request& R) {
   return inplace;
 }
 
+// The work lists, their counters and the level totals: room for n_big /
+// n_local / n_local2 entries to start with, 1024 at least (run_level grows
+// them for its children).
+int ensure_lists(Workspace* W, size_t n_big, size_t n_local, size_t n_local2) {
+  const size_t least = 1024;
+  SRS_TRY(ensure(W->big[0], std::max(least, n_big) * sizeof(Seg)));
+  SRS_TRY(ensure(W->big[1], least * sizeof(Seg)));
+  SRS_TRY(ensure(W->local, std::max(least, n_local) * sizeof(Seg)));
+  SRS_TRY(ensure(W->local2, std::max(least, n_local2) * sizeof(Seg)));
+  SRS_TRY(ensure(W->copy, least * sizeof(Seg)));
+  SRS_TRY(ensure(W->ctr, sizeof(ListCounters)));
+  SRS_TRY(ensure(W->totals, 4 * sizeof(uint64_t)));
+  return SRS_OK;
+}
+
+// ---- the list driver: a sort whose segments its caller lists ------------------
+// Begin: the descriptor of Q's dense SoA columns, *d, and its device copy,
+// *d_desc (uploaded on st). levels: some segment is larger than kLocalCap, so
+// the levels scatter through TMP (grown only then; the LDS chain alone touches
+// IN and OUT only). Threshold 0: canon_zero and leaf_skip stay 0.
+int list_begin(Workspace* W, const Request& Q, bool inplace, bool levels, hipStream_t st,
+               SortDesc* d, SortDesc** d_desc) {
+  *d = init_desc(Q.kind, Q.up);
+  std::vector<size_t> tmp_off;
+  const size_t tmp_bytes = col_offsets(Q.num, Q.ncols, Q.widths, &tmp_off);
+  if (levels) SRS_TRY(ensure(W->tmp, tmp_bytes, ws_alloc_mode(), true));
+  set_columns(Q, *d, levels ? (char*)W->tmp.p : nullptr, nullptr, false, 0, tmp_off.data(),
+              inplace);
+  d->stamp_acc = g_stamp_acc;
+  d->lb_status = g_lb_status;
+  d->lb_err = g_lb_err;
+  SRS_TRY(ensure(W->desc, sizeof(SortDesc)));
+  *d_desc = (SortDesc*)W->desc.p;
+  launch_set_desc(*d, *d_desc, st);
+  return SRS_OK;
+}
+
+// Finish: general levels from S until no large segment is left (`level`: the
+// levels the caller has run already), then the lists' tail. *readbacks (or
+// null) grows by each level's host waits: its totals, unless it is sized
+// from a known length, and its counters.
+int list_finish(Workspace* W, const Request& Q, const SortDesc& d, const SortDesc* d_desc,
+                LevelState S, int level, bool aos_cols, int64_t* readbacks, hipStream_t st) {
+  const int ksl = key_size_of(Q.kind) | (d.canon_zero ? SRS_KS_CANON : 0);  // kernel dispatch key
+  while (S.nbig > 0) {
+    if (++level > 80) return fail(SRS_ERR_INTERNAL, "level limit exceeded");
+    if (readbacks) *readbacks += (S.nbig == 1 && S.known_len >= 0) ? 1 : 2;
+    SRS_TRY(run_level(W, ksl, d_desc, S, st));
+  }
+  return run_lists_tail(W, Q, d, d_desc, S.n_local, S.n_local2, S.n_copy, aos_cols, st);
+}
+
+namespace {
 // The stream's slot for the single-launch sorts' fallback flags
 // (srs_debug_last_fallbacks). A caller that sorts on ever new streams would
 // grow the map without bound: past 64 streams the slots are dropped after a
@@ -1356,8 +1271,6 @@ int plan_range_level(Workspace* W, const Request& R, const std::vector<KeyCluste
   return SRS_OK;
 }
 
-int copy_through(const Request& R, hipStream_t st);
-
 // the home write (choose_layout): below this a sort's columns stay in the
 // L2 / Infinity Cache and the placement of OUT does not matter
 constexpr int64_t kHomeTmp2MinN = int64_t(1) << 24;
@@ -1377,25 +1290,6 @@ int wait_mid_flag(const MidFlag* f, unsigned long long seq, hipStream_t st) {
     }
     cpu_relax();
   }
-  return SRS_OK;
-}
-
-int run_lists_tail(Workspace* W, const Request& R, const SortDesc& d, const SortDesc* d_desc,
-                   int64_t n_local, int64_t n_local2, int64_t n_copy, bool aos_cols,
-                   hipStream_t st);
-
-// The work lists, their counters and the level totals: room for n_big /
-// n_local / n_local2 entries to start with, 1024 at least (run_level grows
-// them for its children).
-int ensure_lists(Workspace* W, size_t n_big, size_t n_local, size_t n_local2) {
-  const size_t least = 1024;
-  SRS_TRY(ensure(W->big[0], std::max(least, n_big) * sizeof(Seg)));
-  SRS_TRY(ensure(W->big[1], least * sizeof(Seg)));
-  SRS_TRY(ensure(W->local, std::max(least, n_local) * sizeof(Seg)));
-  SRS_TRY(ensure(W->local2, std::max(least, n_local2) * sizeof(Seg)));
-  SRS_TRY(ensure(W->copy, least * sizeof(Seg)));
-  SRS_TRY(ensure(W->ctr, sizeof(ListCounters)));
-  SRS_TRY(ensure(W->totals, 4 * sizeof(uint64_t)));
   return SRS_OK;
 }
 
@@ -1793,12 +1687,12 @@ int run_sort(Workspace* W, const Request& R, hipStream_t st) {
   const SortRun X{W, R, d, (SortDesc*)W->desc.p, ksl, inplace ? BUF_OUT : BUF_IN, st};
 
   // ---- the first work lists ---------------------------------------------------
-  LevelState S{0, 0, 0, 0, 0, d.ncols, d.tmp2};
+  LevelState T{0, 0, 0, 0, 0, d.ncols, d.tmp2};
   bool done = false;
-  SRS_TRY(start_lists(X, L, S, &done));
+  SRS_TRY(start_lists(X, L, T, &done));
   if (done) return SRS_OK;
-  S.pair_tiles = pair_tiles_mode(d, ks, L.aos_cols);
-  S.row_offs = pair_row_offs_knob();
+  LevelState S = level_state(d, ks, L.aos_cols, T.nbig, T.n_local, T.n_local2, T.n_copy,
+                             T.known_len);
 
   // ---- the levels: stripe pair or table level, then general levels ------------
   bool stripes = false;
@@ -1813,11 +1707,7 @@ int run_sort(Workspace* W, const Request& R, hipStream_t st) {
     m0.home = F.ranges_final;  // (single-valued buckets: written home directly)
     SRS_TRY(run_level(W, ksl, X.d_desc, S, st, m0));
   }
-  while (S.nbig > 0) {
-    if (++level > 80) return fail(SRS_ERR_INTERNAL, "level limit exceeded");
-    SRS_TRY(run_level(W, ksl, X.d_desc, S, st));
-  }
-  return run_lists_tail(W, R, d, X.d_desc, S.n_local, S.n_local2, S.n_copy, L.aos_cols, st);
+  return list_finish(W, R, d, X.d_desc, S, level, L.aos_cols, nullptr, st);
 }
 
 // The end of every sort that went through the work lists: the LDS chain over
@@ -2018,17 +1908,6 @@ int validate_common(int64_t num, int kind) {
   return SRS_OK;
 }
 
-int copy_through(const Request& R, hipStream_t st) {
-  // num <= 1 with distinct output arrays: the result is the input
-  const int64_t n = R.num < 0 ? 0 : R.num;
-  for (int c = 0; c < R.ncols; c++) {
-    if (R.in_cols[c] == R.out_cols[c] || n == 0) continue;
-    const size_t w = R.aos ? R.elem_size : R.widths[c];
-    HIP_TRY(hipMemcpyAsync(R.out_cols[c], R.in_cols[c], n * w, hipMemcpyDeviceToDevice, st));
-  }
-  return SRS_OK;
-}
-
 // CmpSorterNoSort with num <= cmpSortThreshold: the whole input is one leaf,
 // which the reference leaves as it is (radixSort.hpp:1743, cmp_sorters.hpp:66-78)
 bool whole_input_is_unsorted_leaf(const Request& R) {
@@ -2045,60 +1924,17 @@ int sort_device(Request& R, hipStream_t st) {
   SRS_TRY(ws.begin(st));
   return run_sort(ws.W, R, st);
 }
+}  // namespace
 
-// ---------------------------------------------------------------------------
-// top-k: select the records that can be among the first k by
-// walking down the key's digits, compact them in input order, sort that set
-// ---------------------------------------------------------------------------
-// The select stops refining once the boundary bucket holds this many
-// records: the finishing sort of k + 2^20 records of a small k is then the
-// single-launch sort (kMidMaxKeys), ~0.1 ms, where one more pass would read
-// the whole key column again (srs_debug_set_topk_candidates).
-constexpr int64_t kTopkCandidates = kMidMaxKeys;
-std::atomic<int64_t> g_topk_candidates{kTopkCandidates};
-// Above k = num / 2 the select saves less than it costs: those calls sort
-// everything. Measured at 1e9 u64 + u64 records the two routes cross at
-// k = 0.52-0.54 num (the byte model, 24 n + 176 k against the
-// sort's 112 n + 32 k, said 0.61); at num / 2 the select still wins by 3-6 %.
-// Inputs of one local sort (num <= kLocalCap) are sorted whole as well.
-constexpr int64_t kTopkFullPercent = 50;
-// (SRS_TOPK_FULL_PCT overrides the percentage, for crossover measurements:
-// tools/topk_bench.py; read on every call)
-int64_t topk_full_percent() { return knob_int("SRS_TOPK_FULL_PCT", kTopkFullPercent); }
-
-// The columns a top-k call moves, with their views in the input and in the
-// caller's output: SoA columns as they are; an AoS record as its key and the
-// rest of its bytes in aligned power-of-two pieces of up to 8 bytes, so that
-// the compact set is always SoA columns with the key column first.
-struct TopkLayout {
-  int nc = 0;
-  uint32_t width[SRS_MAX_COLS];
-  char* in[SRS_MAX_COLS];
-  char* out[SRS_MAX_COLS];
-  uint32_t stride[SRS_MAX_COLS];  // of both views
-};
-
-void topk_layout(const Request& R, TopkLayout& L) {
-  if (!R.aos) {
-    L.nc = R.ncols;
-    for (int c = 0; c < R.ncols; c++) {
-      L.width[c] = L.stride[c] = R.widths[c];
-      L.in[c] = (char*)R.in_cols[c];
-      L.out[c] = (char*)R.out_cols[c];
-    }
-    return;
+int copy_through(const Request& R, hipStream_t st) {
+  // num <= 1 with distinct output arrays: the result is the input
+  const int64_t n = R.num < 0 ? 0 : R.num;
+  for (int c = 0; c < R.ncols; c++) {
+    if (R.in_cols[c] == R.out_cols[c] || n == 0) continue;
+    const size_t w = R.aos ? R.elem_size : R.widths[c];
+    HIP_TRY(hipMemcpyAsync(R.out_cols[c], R.in_cols[c], n * w, hipMemcpyDeviceToDevice, st));
   }
-  const uint32_t E = R.elem_size;
-  uint32_t off = 0, w = (uint32_t)key_size_of(R.kind);
-  while (off < E) {
-    L.width[L.nc] = w;
-    L.stride[L.nc] = E;
-    L.in[L.nc] = (char*)R.in_cols[0] + off;
-    L.out[L.nc] = (char*)R.out_cols[0] + off;
-    L.nc++;
-    off += w;
-    w = std::min<uint32_t>(8, off & (~off + 1));  // (E is a power of two: never past the record)
-  }
+  return SRS_OK;
 }
 
 // A sort under the caller's workspace lock and WsUse, on the same stream
@@ -2109,643 +1945,23 @@ int sort_locked(Workspace* W, const Request& R, hipStream_t st) {
   return run_sort(W, R, st);
 }
 
-// The gather's descriptor (W->seldesc): d's first nc columns, the key first.
-void set_gather_desc(Workspace* W, SortDesc& d, int nc, hipStream_t st) {
-  d.key = d.cols[0];
-  d.ncols = nc;
-  launch_set_desc(d, (SortDesc*)W->seldesc.p, st);
+// Device columns are read and written as whole 1/2/4/8-byte words, so every
+// device pointer must be aligned to its word (hipMalloc and torch allocations
+// always are); host arrays may be unaligned, as in the reference (loadu,
+// src/simd.hpp): they are staged through HBM. (rows: the row-wise message)
+int check_col_alignment(const Request& R, int c, bool rows) {
+  const uint32_t al = R.aos ? (R.elem_size < 8 ? R.elem_size : 8) : R.widths[c];
+  if (((uintptr_t)R.in_cols[c] | (uintptr_t)R.out_cols[c]) % al == 0) return SRS_OK;
+  return fail(SRS_ERR_INVALID_ARG, rows ? "device arrays must be aligned to their element size"
+                                        : "device arrays must be aligned to their element size "
+                                          "(records: to min(elem_size, 8))");
 }
 
-// (under the caller's workspace lock and WsUse)
-int topk_locked(Workspace* W, const Request& R, int64_t k, int64_t* idx_out, hipStream_t st) {
-  const int64_t n = R.num;
-  k = std::min(k, n);
-  const int ks = key_size_of(R.kind);
-  const bool full = n <= kLocalCap || (__int128)k * 100 > (__int128)n * topk_full_percent();
-  if (k >= n && !idx_out) {  // the plain out-of-place sort
-    W->topk_info[0] = 0;
-    W->topk_info[1] = n;
-    W->topk_info[2] = 1;
-    return sort_locked(W, R, st);
-  }
-  TopkLayout L;
-  topk_layout(R, L);
-  SortDesc kd = init_desc(R.kind, R.up);
-  SelectArgs a;
-  memset(&a, 0, sizeof a);
-  a.keys = L.in[0];
-  a.stride = L.stride[0];
-  a.n = n;
-  a.all = 1;
-  a.key_bits = kd.key_bits;
-  a.mpos = kd.mpos;
-  a.mneg = kd.mneg;
-
-  // ---- which records: the prefix of the boundary bucket ---------------------
-  int64_t passes = 0, limit = n;  // limit: records the compact set holds
-  if (!full) {
-    SRS_TRY(ensure(W->selhist, kSelHistWords * sizeof(uint64_t)));
-    if (!W->h_sel)
-      HIP_TRY(hipHostMalloc((void**)&W->h_sel, kSelHistWords * sizeof(uint64_t), hipHostMallocDefault));
-    const int kb = kd.key_bits;
-    const uint64_t kmask = kb == 64 ? ~0ull : ((1ull << kb) - 1);
-    const int64_t maxc = g_topk_candidates.load();
-    uint64_t prefix = 0;  // the fixed top bits, in place
-    int fixed = 0, top = kb;  // the next digit ends below bit `top`
-    int64_t k_rem = k, cand = n;  // the rank wanted inside the prefix's bucket; its size
-    bool resolved = false;        // the bucket's keys are all equal
-    for (;;) {
-      a.bits = std::min(kHistMaxBits, top);
-      a.shift = top - a.bits;
-      a.all = fixed == 0;
-      a.psh = fixed ? kb - fixed : 0;
-      a.pv = fixed ? prefix >> a.psh : 0;
-      HIP_TRY(hipMemsetAsync(W->selhist.p, 0, kSelHistWords * sizeof(uint64_t), st));
-      {
-        TimedScope ts("select_hist", (double)n, st);
-        launch_select_hist(ks, a, (unsigned long long*)W->selhist.p, st);
-      }
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(W->h_sel, W->selhist.p, kSelHistWords * sizeof(uint64_t),
-                             hipMemcpyDeviceToHost, st));
-      SRS_TRY(sync_poll(st));
-      passes++;
-      const unsigned long long* h = W->h_sel;
-      int64_t below = 0;
-      int b = 0;
-      const int nb = 1 << a.bits;
-      for (; b < nb; b++) {
-        if (below + (int64_t)h[b] >= k_rem) break;
-        below += (int64_t)h[b];
-      }
-      if (b == nb) return fail(SRS_ERR_INTERNAL, "top-k: the histogram holds fewer keys than its bucket");
-      k_rem -= below;
-      cand = (int64_t)h[b];
-      prefix |= (uint64_t)b << a.shift;
-      fixed = kb - a.shift;
-      // where the bucket's parent still varies below this digit: the next
-      // digit starts at its highest varying bit, the bits between are shared
-      const uint64_t low = (1ull << a.shift) - 1;  // (shift <= 52)
-      const uint64_t vand = ~h[kSelOrSlot + 1] & kmask;
-      const uint64_t var = (h[kSelOrSlot] ^ vand) & low;
-      if (var == 0) {
-        resolved = true;
-        prefix |= vand & low;
-        fixed = kb;
-      }
-      if (resolved || cand == k_rem || cand <= maxc) break;
-      const int hb = 63 - __builtin_clzll(var);
-      prefix |= vand & low & ~((2ull << hb) - 1);
-      fixed = kb - (hb + 1);
-      top = hb + 1;
-    }
-    a.all = 0;
-    a.psh = kb - fixed;
-    a.pv = prefix >> a.psh;
-    // everything below the prefix, and the bucket itself (a bucket of equal
-    // keys: only its first k_rem records, in input order)
-    limit = (k - k_rem) + (resolved ? k_rem : cand);
-  }
-  const int64_t m = limit;
-
-  // ---- the compact columns ---------------------------------------------------
-  const int nsc = L.nc + (idx_out ? 1 : 0);
-  size_t off[SRS_MAX_COLS + 1], bytes = 0;
-  for (int c = 0; c < nsc; c++) {
-    off[c] = bytes;
-    bytes += align_up((size_t)m * (c < L.nc ? L.width[c] : 8), 256);
-  }
-  SRS_TRY(ensure(W->sel, bytes, ws_alloc_mode()));
-  SRS_TRY(ensure(W->seldesc, sizeof(SortDesc)));
-  char* sel = (char*)W->sel.p;
-  int64_t* sel_idx = idx_out ? (int64_t*)(sel + off[L.nc]) : nullptr;
-  Request S;  // the compact set's sort, in place
-  S.num = m;
-  S.kind = R.kind;
-  S.up = R.up;
-  S.thresh = 0;  // (the total order for floats at every size)
-  S.aos = false;
-  S.elem_size = 0;
-  S.ncols = nsc;
-  for (int c = 0; c < nsc; c++) {
-    S.in_cols[c] = S.out_cols[c] = sel + off[c];
-    S.widths[c] = c < L.nc ? L.width[c] : 8;
-  }
-  W->topk_info[0] = passes;
-  W->topk_info[1] = m;
-  W->topk_info[2] = full ? 1 : 0;
-
-  if (full && !R.aos && !idx_out) {
-    // SoA columns: sorted straight into the compact columns
-    Request F = R;
-    F.thresh = 0;
-    for (int c = 0; c < nsc; c++) F.out_cols[c] = S.out_cols[c];
-    SRS_TRY(sort_locked(W, F, st));
-  } else {
-    SortDesc d = init_desc(R.kind, R.up);
-    for (int c = 0; c < L.nc; c++)
-      d.cols[c] = Col{{L.in[c], sel + off[c], nullptr, nullptr}, L.width[c],
-                      {L.stride[c], L.width[c], L.width[c], L.width[c]}};
-    set_gather_desc(W, d, L.nc, st);
-    const uint64_t* tbase = nullptr;
-    if (!full) {
-      const int64_t ntiles = (n + kTile - 1) / kTile;
-      const int64_t rows = 2 * ntiles;
-      SRS_TRY(ensure(W->selcnt, (size_t)(2 * rows + scan_temp_elems(rows) + 1) * sizeof(uint64_t)));
-      uint64_t* counts = (uint64_t*)W->selcnt.p;
-      uint64_t* bases = counts + rows;
-      uint64_t* temp = bases + rows;
-      {
-        TimedScope ts("select_tally", (double)n, st);
-        launch_select_tally(ks, a, counts, st);
-      }
-      launch_excl_scan(counts, bases, rows, temp, temp + scan_temp_elems(rows), st);
-      tbase = bases;
-    }
-    {
-      TimedScope ts("select_gather", (double)m, st);
-      launch_select_gather(ks, a, (const SortDesc*)W->seldesc.p, tbase, limit, sel_idx, st);
-    }
-    HIP_TRY(hipGetLastError());
-    SRS_TRY(sort_locked(W, S, st));
-  }
-
-  // ---- the first k records to the caller's arrays ----------------------------
-  SortDesc d = init_desc(R.kind, R.up);
-  for (int c = 0; c < nsc; c++) {
-    const uint32_t w = S.widths[c];
-    char* out = c < L.nc ? L.out[c] : (char*)idx_out;
-    d.cols[c] = Col{{sel + off[c], out, nullptr, nullptr}, w, {w, c < L.nc ? L.stride[c] : 8u, w, w}};
-  }
-  set_gather_desc(W, d, nsc, st);
-  SelectArgs f = a;
-  f.keys = sel;
-  f.stride = (uint32_t)ks;
-  f.n = k;
-  f.all = 1;
-  {
-    TimedScope ts("select_gather", (double)k, st);
-    launch_select_gather(ks, f, (const SortDesc*)W->seldesc.p, nullptr, k, nullptr, st);
-  }
-  HIP_TRY(hipGetLastError());
+namespace {
+// (the sorts: alignment only, and nothing to check of num <= 1 records)
+int check_device_alignment(const Request& R) {
+  for (int c = 0; c < R.ncols && R.num > 1; c++) SRS_TRY(check_col_alignment(R, c, false));
   return SRS_OK;
-}
-
-int topk_device(const Request& R, int64_t k, int64_t* idx_out, hipStream_t st) {
-  WsScope ws;
-  SRS_TRY(ws.begin(st));
-  return topk_locked(ws.W, R, k, idx_out, st);
-}
-
-bool ranges_overlap(const void* a, size_t an, const void* b, size_t bn) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return an && bn && x < y + bn && y < x + an;
-}
-
-// What the device entry points check of their arrays, all before the first
-// device access. Device columns are read and written as whole 1/2/4/8-byte
-// words, so every device pointer must be aligned to its word (hipMalloc and
-// torch allocations always are); host arrays may be unaligned, as in the
-// reference (loadu, src/simd.hpp): they are staged through HBM.
-// what NULL (the sorts, which may run in place): alignment only. Else (the
-// out-of-place calls, "top-k" / "sort rows"): the column count with
-// indices_out; then, unless out_recs <= 0 (the call will do nothing), the
-// caller's shape error if any, NULL arrays, alignment (rows: the row-wise
-// calls' message), and the outputs' out_recs records clear of the inputs'
-// in_recs.
-int validate_outputs(const Request& R, const char* what = nullptr, const void* out0 = nullptr,
-                     const int64_t* idx_out = nullptr, int64_t in_recs = 0, int64_t out_recs = 0,
-                     bool rows = false, const char* shape_err = nullptr) {
-  if (what) {
-    if (idx_out && !R.aos && R.ncols - 1 > SRS_MAX_PAYLOADS - 1)
-      return fail(SRS_ERR_UNSUPPORTED,
-                  "indices_out travels as one more payload column: at most 63 payload columns "
-                  "with it");
-    if (out_recs <= 0) return SRS_OK;
-    if (shape_err) return fail(SRS_ERR_INVALID_ARG, shape_err);
-    if (!R.in_cols[0]) return fail(SRS_ERR_INVALID_ARG, R.aos ? "elements is NULL" : "keys is NULL");
-    if (!out0) return fail(SRS_ERR_INVALID_ARG, R.aos ? "elements_out is NULL" : "keys_out is NULL");
-  }
-  for (int c = 0; c < R.ncols; c++) {
-    if (what && (!R.in_cols[c] || !R.out_cols[c]))
-      return fail(SRS_ERR_INVALID_ARG, "payload pointer is NULL");
-    const uint32_t al = R.aos ? (R.elem_size < 8 ? R.elem_size : 8) : R.widths[c];
-    if (((uintptr_t)R.in_cols[c] | (uintptr_t)R.out_cols[c]) % al != 0)
-      return fail(SRS_ERR_INVALID_ARG,
-                  rows ? "device arrays must be aligned to their element size"
-                       : "device arrays must be aligned to their element size "
-                         "(records: to min(elem_size, 8))");
-  }
-  if (!what) return SRS_OK;
-  if ((uintptr_t)idx_out % 8 != 0) return fail(SRS_ERR_INVALID_ARG, "indices_out must be 8-byte aligned");
-  for (int o = 0; o <= R.ncols; o++) {
-    const void* op = o < R.ncols ? R.out_cols[o] : (const void*)idx_out;
-    const size_t ob = (size_t)out_recs * (o < R.ncols ? R.widths[o] : 8);
-    if (!op) continue;
-    for (int c = 0; c < R.ncols; c++)
-      if (ranges_overlap(op, ob, R.in_cols[c], (size_t)in_recs * R.widths[c]))
-        return fail(SRS_ERR_INVALID_ARG,
-                    std::string(what) + " outputs must not overlap the inputs");
-  }
-  return SRS_OK;
-}
-
-// (the sorts: nothing to check of num <= 1 records)
-int check_device_alignment(const Request& R) { return R.num <= 1 ? SRS_OK : validate_outputs(R); }
-
-int topk_validate(const Request& R, int64_t k, const void* out0, const int64_t* idx_out) {
-  return validate_outputs(R, "top-k", out0, idx_out, R.num, std::min(k, R.num));
-}
-
-// ---------------------------------------------------------------------------
-// row-wise top-k: the first k records of every row of a
-// matrix. Rows that fit one workgroup's registers (resident) and longer rows
-// with k <= kTopkRowsMaxK (stream) take one launch, a workgroup per row, with
-// nothing read back; everything else goes row by row through topk_locked.
-// ---------------------------------------------------------------------------
-enum { ROWS_RESIDENT = 0, ROWS_STREAM = 1, ROWS_LOOP = 2 };
-std::atomic<int> g_topk_rows_route{-1};  // srs_debug_set_topk_rows_route
-// The stream route puts one workgroup on a row, so a few very long rows leave
-// most of the chip idle while the loop's select runs each row on all of it.
-// Measured (tools/topk_rows_bench.py --sweep): the routes
-// cross at 11-16 rows of 2^20 records, 35-49 of 2^22, 116-129 of 2^24 and
-// ~350 of 2^26, i.e. near 12 * (row_len / 2^20)^0.8 rows; below that many
-// rows the loop is taken. Rows shorter than 2^20 were not measured: stream.
-constexpr int64_t kTopkRowsLoopLen = int64_t(1) << 20;
-bool topk_rows_prefers_loop(int64_t rows, int64_t row_len) {
-  if (row_len < kTopkRowsLoopLen) return false;
-  return (double)rows < 12.0 * std::pow((double)row_len / (double)kTopkRowsLoopLen, 0.8);
-}
-
-// R describes one row (R.num = row_len; the columns point at row 0).
-// (what: the caller's name for its outputs in the overlap message; the
-// row-wise sort validates through this too, with kk = row_len)
-int topk_rows_validate(const Request& R, int64_t rows, int64_t row_stride, int64_t kk,
-                       const void* out0, const int64_t* idx_out, const char* what = "top-k") {
-  const bool work = rows > 0 && R.num > 0 && kk > 0;
-  int64_t cells = 0;
-  const char* shape = row_stride < R.num ? "row_stride < row_len"
-                      : __builtin_mul_overflow(rows, row_stride, &cells) || cells > (INT64_MAX >> 4)
-                          ? "rows * row_stride overflows"
-                          : nullptr;
-  if (!work || shape) return validate_outputs(R, what, out0, idx_out, 0, work, true, shape);
-  return validate_outputs(R, what, out0, idx_out, (rows - 1) * row_stride + R.num, rows * kk, true);
-}
-
-// The one-launch routes' kernel (launch_topk_rows): the first kk records of
-// every row's sorted order, kk <= row_len (kk == row_len: the rows sorted
-// whole). pass: the buffer of the kernel's pass counter.
-int launch_rows_kernel(DevBuf& pass, const Request& R, int64_t rows, int64_t row_stride,
-                       int64_t kk, int64_t* idx_out, bool stream, hipStream_t st) {
-  SRS_TRY(ensure(pass, sizeof(unsigned long long)));
-  HIP_TRY(hipMemsetAsync(pass.p, 0, sizeof(unsigned long long), st));
-  SortDesc kd = init_desc(R.kind, R.up);
-  TopkRowsArgs a;
-  memset(&a, 0, sizeof a);
-  a.rows = rows;
-  a.row_len = R.num;
-  a.row_stride = row_stride;
-  a.kk = kk;
-  a.ncols = R.ncols;
-  a.key_bits = kd.key_bits;
-  a.mpos = kd.mpos;
-  a.mneg = kd.mneg;
-  a.idx_out = idx_out;
-  a.max_passes = (unsigned long long*)pass.p;
-  for (int c = 0; c < R.ncols; c++)
-    a.col[c] = TopkRowsCol{(const char*)R.in_cols[c], (char*)R.out_cols[c], R.widths[c]};
-  {
-    TimedScope ts("topk_rows", (double)rows * (double)R.num, st);
-    HIP_TRY(launch_topk_rows(key_size_of(R.kind), a, stream, st));
-  }
-  return SRS_OK;
-}
-
-int topk_rows_device(const Request& R, int64_t rows, int64_t row_stride, int64_t k,
-                     int64_t* idx_out, hipStream_t st) {
-  const int64_t n = R.num, kk = std::min(k, n);
-  const bool can_resident = n <= kLocalCap;
-  const bool can_stream = !can_resident && kk <= kTopkRowsMaxK && n < (int64_t(1) << 31);
-  int route = g_topk_rows_route.load();
-  if (route < 0) {
-    route = can_resident ? ROWS_RESIDENT
-            : can_stream && !topk_rows_prefers_loop(rows, n) ? ROWS_STREAM
-                                                                                  : ROWS_LOOP;
-  } else if (route == ROWS_RESIDENT && !can_resident) {
-    return fail(SRS_ERR_UNSUPPORTED, "top-k rows: the resident route takes row_len <= 8192");
-  } else if (route == ROWS_STREAM && !can_stream) {
-    return fail(SRS_ERR_UNSUPPORTED,
-                "top-k rows: the stream route takes 8192 < row_len < 2^31 and min(k, row_len) <= "
-                "kTopkRowsMaxK");
-  }
-  WsScope ws;
-  SRS_TRY(ws.begin(st));
-  Workspace* W = ws.W;
-  int64_t* info = W->topk_rows_info;
-  info[0] = route;
-  info[1] = info[2] = info[3] = 0;
-
-  if (route == ROWS_LOOP) {
-    // correct and slow: every row is one single-array top-k, with its select
-    // passes' read-backs (info[1]: its launches are not counted)
-    info[1] = -1;
-    for (int64_t r = 0; r < rows; r++) {
-      Request Q = R;
-      for (int c = 0; c < R.ncols; c++) {
-        Q.in_cols[c] = (char*)R.in_cols[c] + r * row_stride * (int64_t)R.widths[c];
-        Q.out_cols[c] = (char*)R.out_cols[c] + r * kk * (int64_t)R.widths[c];
-      }
-      SRS_TRY(topk_locked(W, Q, k, idx_out ? idx_out + r * kk : nullptr, st));
-      info[2] = std::max(info[2], W->topk_info[0]);
-      info[3] += W->topk_info[0];
-    }
-    W->rows_pass_pending = false;
-    return SRS_OK;
-  }
-
-  SRS_TRY(launch_rows_kernel(W->rowspass, R, rows, row_stride, kk, idx_out, route == ROWS_STREAM,
-                             st));
-  info[1] = 1;
-  W->rows_pass_pending = true;
-  return SRS_OK;
-}
-
-// ---------------------------------------------------------------------------
-// row-wise sort: every row of a matrix sorted, out of place.
-// Route 0 is the rows kernel above with kk = row_len; routes 1 and 2 make the
-// rows segments of the sort's work lists on the device (launch_rows_segs) and
-// run the sort's own LDS chain / global levels over them.
-// ---------------------------------------------------------------------------
-enum { SORT_ROWS_KERNEL = 0, SORT_ROWS_LOCAL = 1, SORT_ROWS_LEVELS = 2 };
-std::atomic<int> g_sort_rows_route{-1};  // srs_debug_set_sort_rows_route
-// Rows of 257 .. kLocalCap records: the rows kernel below this length, the
-// local lists from it. Measured at 2^26 records (tools/sort_rows_bench.py
-// --sweep): the rows kernel sorts a row padded to a power of
-// two and wins at 1024 records and below on every column set; from 1025 the
-// chain's direct kernel (a 4- or 8-byte key and one 8-byte payload, no index
-// column) wins at every length measured, 1.13x at 1025 to 3.2x at 8192. The
-// chain's general kernel, which every other column set takes, wins once the
-// rows kernel pads past 4096 records (2.1x at 4097) but loses 1.5-2.3x at
-// 1152-2048: those sets cross at kSortRowsLocalMinGeneral.
-constexpr int64_t kSortRowsLocalMin = 1025;
-constexpr int64_t kSortRowsLocalMinGeneral = kLocalCapSmall + 1;
-int64_t sort_rows_local_min(const Request& R, bool with_indices) {
-  const int ks = key_size_of(R.kind);
-  const bool direct = !with_indices && R.ncols == 2 && R.widths[1] == 8 && (ks == 4 || ks == 8);
-  return direct ? kSortRowsLocalMin : kSortRowsLocalMinGeneral;
-}
-
-// Routes 1 and 2. Q is the whole matrix as one request of dense columns
-// (Q.num = rows * row_len; the index column, when asked for, is its last
-// payload): in place on the outputs after the prepare pass (IN aliases OUT,
-// the segments start in OUT), or out of place from the caller's dense input
-// (the segments start in IN). *readbacks: host waits of the levels.
-int sort_rows_lists(Workspace* W, const Request& Q, int64_t rows, int64_t row_len,
-                    int64_t* readbacks, hipStream_t st) {
-  W->last_small = false;
-  const int ks = key_size_of(Q.kind);
-  const int64_t n = Q.num;
-  const bool inplace = is_inplace(Q);
-  const bool levels = row_len > kLocalCap;
-  SortDesc d = init_desc(Q.kind, Q.up);  // (threshold 0: canon_zero and leaf_skip stay 0)
-  // the levels scatter through TMP; the LDS chain alone touches IN and OUT only
-  std::vector<size_t> tmp_off;
-  const size_t tmp_bytes = col_offsets(n, Q.ncols, Q.widths, &tmp_off);
-  char* tmp = nullptr;
-  if (levels) {
-    SRS_TRY(ensure(W->tmp, tmp_bytes, ws_alloc_mode(), true));
-    tmp = (char*)W->tmp.p;
-  }
-  set_columns(Q, d, tmp, nullptr, false, 0, tmp_off.data(), inplace);
-  d.stamp_acc = g_stamp_acc;
-  d.lb_status = g_lb_status;
-  d.lb_err = g_lb_err;
-  SRS_TRY(ensure(W->desc, sizeof(SortDesc)));
-  SortDesc* d_desc = (SortDesc*)W->desc.p;
-
-  // ---- the lists: one segment per row, all in one list ----------------------
-  const int cls = levels ? 2 : row_len > kLocalCapSmall ? 1 : 0;
-  SRS_TRY(ensure_lists(W, cls == 2 ? rows : 0, cls == 0 ? rows : 0, cls == 1 ? rows : 0));
-  ListCounters* d_ctr = (ListCounters*)W->ctr.p;
-  Seg* list = (Seg*)(cls == 2 ? W->big[0].p : cls == 1 ? W->local2.p : W->local.p);
-  launch_set_desc(d, d_desc, st);
-  HIP_TRY(launch_rows_segs(list, rows, row_len, d.key_bits, inplace ? BUF_OUT : BUF_IN, cls, d_ctr,
-                           st));
-  W->h_ctr->local_elems = levels ? 0 : (uint64_t)n;
-
-  LevelState S{cls == 2 ? rows : 0, cls == 0 ? rows : 0, cls == 1 ? rows : 0, 0, 0, d.ncols,
-               d.tmp2};
-  S.pair_tiles = pair_tiles_mode(d, ks, false);
-  S.row_offs = pair_row_offs_knob();
-  if (S.nbig == 1) S.known_len = row_len;
-  int level = 0;
-  while (S.nbig > 0) {
-    if (++level > 80) return fail(SRS_ERR_INTERNAL, "level limit exceeded");
-    *readbacks += (S.nbig == 1 && S.known_len >= 0) ? 1 : 2;  // (totals, counters)
-    SRS_TRY(run_level(W, ks, d_desc, S, st));
-  }
-  return run_lists_tail(W, Q, d, d_desc, S.n_local, S.n_local2, S.n_copy, false, st);
-}
-
-// R describes one row (R.num = row_len; the columns point at row 0).
-int sort_rows_device(const Request& R, int64_t rows, int64_t row_stride, int64_t* idx_out,
-                     hipStream_t st) {
-  const int64_t len = R.num;
-  int route = g_sort_rows_route.load();
-  if (route < 0) {
-    route = len > kLocalCap ? SORT_ROWS_LEVELS
-            : len <= kRowsWaveMax || len < sort_rows_local_min(R, idx_out != nullptr)
-                ? SORT_ROWS_KERNEL
-                : SORT_ROWS_LOCAL;
-  } else if (route == SORT_ROWS_KERNEL && len > kLocalCap) {
-    return fail(SRS_ERR_UNSUPPORTED, "sort rows: the rows kernel takes row_len <= 8192");
-  } else if (route == SORT_ROWS_LOCAL && (len < 2 || len > kLocalCap)) {
-    return fail(SRS_ERR_UNSUPPORTED, "sort rows: the local lists take 2 <= row_len <= 8192");
-  } else if (route == SORT_ROWS_LEVELS && len <= kLocalCap) {
-    return fail(SRS_ERR_UNSUPPORTED, "sort rows: the levels take row_len > 8192");
-  }
-  WsScope ws;
-  SRS_TRY(ws.begin(st));
-  Workspace* W = ws.W;
-  int64_t* info = W->sort_rows_info;
-  info[0] = route;
-  info[1] = info[2] = info[3] = 0;
-
-  if (route == SORT_ROWS_KERNEL) {
-    SRS_TRY(launch_rows_kernel(W->sortrowspass, R, rows, row_stride, len, idx_out, false, st));
-    info[1] = 1;
-    return SRS_OK;
-  }
-
-  info[1] = -1;  // (the chain's launches are not counted)
-  Request Q = R;
-  Q.num = rows * len;
-  const bool prepare = row_stride != len || idx_out != nullptr;
-  if (prepare) {
-    // strided rows and the index column land dense in the outputs, which are
-    // then sorted in place (no workspace column, and the
-    // in-place segment lists are the ones srs_sort_segments_device runs)
-    RowsPrepareArgs a;
-    memset(&a, 0, sizeof a);
-    a.rows = rows;
-    a.row_len = len;
-    a.row_stride = row_stride;
-    a.ncols = R.ncols;
-    a.idx_out = idx_out;
-    for (int c = 0; c < R.ncols; c++)
-      a.col[c] = TopkRowsCol{(const char*)R.in_cols[c], (char*)R.out_cols[c], R.widths[c]};
-    {
-      TimedScope ts("rows_prepare", (double)Q.num, st);
-      HIP_TRY(launch_rows_prepare(a, st));
-    }
-    info[3] = 1;
-    for (int c = 0; c < Q.ncols; c++) Q.in_cols[c] = Q.out_cols[c];
-    if (idx_out) {
-      Q.in_cols[Q.ncols] = Q.out_cols[Q.ncols] = idx_out;
-      Q.widths[Q.ncols++] = 8;
-    }
-  }
-  return sort_rows_lists(W, Q, rows, len, &info[2], st);
-}
-
-// ---------------------------------------------------------------------------
-// ragged sort: segments [offsets[i], offsets[i + 1]) of dense
-// columns, the offsets on the device. One classify pass (ragged_segs_kernel)
-// lists the segments longer than short_max and counts the bad and the empty
-// ones; its counters come back through W->h_ctr while the short kernel, which
-// owns every segment of 1 .. short_max records, is already queued behind the
-// copy. Listed segments then run the sort's levels and LDS chain exactly as
-// the rows of sort_rows_lists do.
-// ---------------------------------------------------------------------------
-std::atomic<int> g_sort_ragged_short_max{-1};  // srs_debug_set_sort_ragged_short_max
-
-// Host wait for an event with sync_poll's manners.
-int event_poll(hipEvent_t ev) {
-  const auto t0 = std::chrono::steady_clock::now();
-  for (;;) {
-    const hipError_t q = hipEventQuery(ev);
-    if (q == hipSuccess) return SRS_OK;
-    if (q != hipErrorNotReady) HIP_TRY(q);
-    const auto dt = std::chrono::steady_clock::now() - t0;
-    if (dt > std::chrono::milliseconds(20)) break;
-    if (dt < std::chrono::microseconds(200)) cpu_relax();
-    else std::this_thread::yield();
-  }
-  HIP_TRY(hipEventSynchronize(ev));
-  return SRS_OK;
-}
-
-// What ragged_segs_kernel and run_lists_tail may index of the lists: valid
-// offsets list at most num / (short_max + 1) segments, the kernel lists no
-// more than that of any others.
-int64_t ragged_list_cap(int64_t num, int64_t nseg, int short_max) {
-  return std::min(nseg, num / ((int64_t)short_max + 1));
-}
-
-// R: the dense columns (R.num = num records each).
-int sort_ragged_device(const Request& R, int64_t nseg, const int64_t* offsets, int64_t* idx_out,
-                       hipStream_t st) {
-  int short_max = g_sort_ragged_short_max.load();
-  if (short_max < 0) short_max = kRowsWaveMax;
-  const int64_t num = R.num;
-  const int64_t cap = ragged_list_cap(num, nseg, short_max);
-  if ((nseg + 255) / 256 > 0x7fffffff)
-    return fail(SRS_ERR_UNSUPPORTED, "sort ragged: more than 2^39 segments");
-  WsScope ws;
-  SRS_TRY(ws.begin(st));
-  Workspace* W = ws.W;
-  W->last_small = false;
-  int64_t* info = W->sort_ragged_info;
-  for (int i = 0; i < 6; i++) info[i] = 0;
-  const int ks = key_size_of(R.kind);
-  const bool with_idx = idx_out != nullptr;
-  SortDesc d = init_desc(R.kind, R.up);  // (threshold 0: canon_zero and leaf_skip stay 0)
-
-  RaggedArgs a;
-  memset(&a, 0, sizeof a);
-  a.num = num;
-  a.nseg = nseg;
-  a.offsets = offsets;
-  a.ncols = R.ncols;
-  a.key_bits = d.key_bits;
-  a.mpos = d.mpos;
-  a.mneg = d.mneg;
-  a.short_max = short_max;
-  a.idx_out = idx_out;
-  for (int c = 0; c < R.ncols; c++)
-    a.col[c] = TopkRowsCol{(const char*)R.in_cols[c], (char*)R.out_cols[c], R.widths[c]};
-
-  // ---- classify, and the one read-back of the counters ----------------------
-  SRS_TRY(ensure_lists(W, (size_t)cap, (size_t)cap, (size_t)cap));
-  ListCounters* d_ctr = (ListCounters*)W->ctr.p;
-  if (!W->ev_ragged) HIP_TRY(hipEventCreateWithFlags(&W->ev_ragged, hipEventDisableTiming));
-  HIP_TRY(hipMemsetAsync(d_ctr, 0, sizeof(ListCounters), st));
-  {
-    TimedScope ts("ragged_segs", (double)nseg, st);
-    HIP_TRY(launch_ragged_segs(offsets, nseg, num, short_max, d.key_bits,
-                               with_idx ? BUF_OUT : BUF_IN, cap, (Seg*)W->big[0].p,
-                               (Seg*)W->local.p, (Seg*)W->local2.p, (Seg*)W->copy.p, d_ctr, st));
-  }
-  HIP_TRY(hipMemcpyAsync(W->h_ctr, d_ctr, sizeof(ListCounters), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipEventRecord(W->ev_ragged, st));
-  if (short_max > 0) {
-    // (queued behind the copy, so the host's wait below does not include it)
-    TimedScope ts("ragged_short", (double)num, st);
-    HIP_TRY(launch_ragged_short(ks, a, st));
-  }
-  SRS_TRY(event_poll(W->ev_ragged));
-  const ListCounters c = *W->h_ctr;
-  info[4] = 1;
-  info[1] = (int64_t)c.n_local;
-  info[2] = (int64_t)c.n_local2;
-  info[3] = (int64_t)c.n_big;
-  info[0] = nseg - (int64_t)c.n_listed - (int64_t)c.n_empty - (int64_t)c.n_bad;
-  if (c.n_bad > 0)
-    return fail(SRS_ERR_INVALID_ARG,
-                "sort ragged: " + std::to_string(c.n_bad) +
-                    " segment(s) with offsets that decrease or leave [0, num] (skipped; the "
-                    "outputs are unspecified)");
-  if (c.n_listed == 0) return SRS_OK;
-
-  // ---- the listed segments: the sort's levels and LDS chain -----------------
-  // Without indices they sort IN -> OUT; with indices the prepare pass moves
-  // them to the outputs with their iota, and they sort in place there.
-  Request Q = R;
-  if (with_idx) {
-    for (int c2 = 0; c2 < Q.ncols; c2++) Q.in_cols[c2] = Q.out_cols[c2];
-    Q.in_cols[Q.ncols] = Q.out_cols[Q.ncols] = idx_out;
-    Q.widths[Q.ncols++] = 8;
-  }
-  std::vector<size_t> tmp_off;
-  const size_t tmp_bytes = col_offsets(num, Q.ncols, Q.widths, &tmp_off);
-  char* tmp = nullptr;
-  if (c.n_big > 0) {  // the levels scatter through TMP; the LDS chain touches IN and OUT only
-    SRS_TRY(ensure(W->tmp, tmp_bytes, ws_alloc_mode(), true));
-    tmp = (char*)W->tmp.p;
-  }
-  set_columns(Q, d, tmp, nullptr, false, 0, tmp_off.data(), with_idx);
-  d.stamp_acc = g_stamp_acc;
-  d.lb_status = g_lb_status;
-  d.lb_err = g_lb_err;
-  SRS_TRY(ensure(W->desc, sizeof(SortDesc)));
-  SortDesc* d_desc = (SortDesc*)W->desc.p;
-  launch_set_desc(d, d_desc, st);
-  if (with_idx) {
-    TimedScope ts("ragged_prepare", (double)num, st);
-    HIP_TRY(launch_ragged_prepare(a, st));
-    info[5] = 1;
-  }
-  LevelState S{(int64_t)c.n_big, (int64_t)c.n_local, (int64_t)c.n_local2, (int64_t)c.n_copy, 0,
-               d.ncols, d.tmp2};
-  S.pair_tiles = pair_tiles_mode(d, ks, false);
-  S.row_offs = pair_row_offs_knob();
-  int level = 0;
-  while (S.nbig > 0) {
-    if (++level > 80) return fail(SRS_ERR_INTERNAL, "level limit exceeded");
-    info[4] += 2;  // (totals, counters)
-    SRS_TRY(run_level(W, ks, d_desc, S, st));
-  }
-  return run_lists_tail(W, Q, d, d_desc, S.n_local, S.n_local2, S.n_copy, false, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -3254,6 +2470,15 @@ int sort_host(Request& R) {
   return host_sort_single(R, devs.empty() ? dev : devs[0]);
 }
 
+int set_leaf_mode(Request& R, int leaf_mode) {
+  if (leaf_mode != SRS_LEAF_SORTED && leaf_mode != SRS_LEAF_UNSORTED)
+    return fail(SRS_ERR_INVALID_ARG, "leaf_mode must be SRS_LEAF_SORTED or SRS_LEAF_UNSORTED");
+  R.leaf_mode = leaf_mode;
+  return SRS_OK;
+}
+
+}  // namespace
+
 int build_soa(Request& R, int64_t num, int kind, int up, int64_t thresh, void* keys,
               int32_t np, void* const* pays, const uint32_t* sizes, void* keys_out,
               void* const* pays_out) {
@@ -3308,16 +2533,7 @@ int build_aos(Request& R, int64_t num, int kind, int up, int64_t thresh, void* e
   return SRS_OK;
 }
 
-int set_leaf_mode(Request& R, int leaf_mode) {
-  if (leaf_mode != SRS_LEAF_SORTED && leaf_mode != SRS_LEAF_UNSORTED)
-    return fail(SRS_ERR_INVALID_ARG, "leaf_mode must be SRS_LEAF_SORTED or SRS_LEAF_UNSORTED");
-  R.leaf_mode = leaf_mode;
-  return SRS_OK;
-}
-
-}  // namespace
-
-// (other translation units of the library report errors through this)
+// (fail, under the name srs_shard.hip knows it by)
 int set_error(int code, const std::string& msg) { return fail(code, msg); }
 
 void defer_workspace_frees(bool on) { t_defer = on; }
@@ -3446,78 +2662,6 @@ int srs_sort_aos_device(int64_t num, int key_kind, int up, int64_t cmp_sort_thre
                         void* stream) {
   return srs_sort_aos_device_leaf(num, key_kind, up, cmp_sort_threshold, SRS_LEAF_SORTED,
                                   elements, elem_size, elements_out, stream);
-}
-
-int srs_topk_soa_device(int64_t num, int64_t k, int key_kind, int up, const void* keys,
-                        int32_t num_payloads, const void* const* payloads,
-                        const uint32_t* payload_sizes, void* keys_out, void* const* payloads_out,
-                        int64_t* indices_out, void* stream) {
-  Request R;
-  SRS_TRY(build_soa(R, num, key_kind, up, 0, (void*)keys, num_payloads, (void* const*)payloads,
-                    payload_sizes, keys_out, payloads_out));
-  SRS_TRY(topk_validate(R, k, keys_out, indices_out));
-  if (k <= 0 || num <= 0) return SRS_OK;
-  return topk_device(R, k, indices_out, (hipStream_t)stream);
-}
-
-int srs_topk_rows_soa_device(int64_t rows, int64_t row_len, int64_t row_stride, int64_t k,
-                             int key_kind, int up, const void* keys, int32_t num_payloads,
-                             const void* const* payloads, const uint32_t* payload_sizes,
-                             void* keys_out, void* const* payloads_out, int64_t* indices_out,
-                             void* stream) {
-  Request R;
-  SRS_TRY(build_soa(R, row_len, key_kind, up, 0, (void*)keys, num_payloads,
-                    (void* const*)payloads, payload_sizes, keys_out, payloads_out));
-  SRS_TRY(topk_rows_validate(R, rows, row_stride, std::min(k, row_len), keys_out, indices_out));
-  if (rows <= 0 || row_len <= 0 || k <= 0) return SRS_OK;
-  return topk_rows_device(R, rows, row_stride, k, indices_out, (hipStream_t)stream);
-}
-
-int srs_sort_rows_soa_device(int64_t rows, int64_t row_len, int64_t row_stride, int key_kind,
-                             int up, const void* keys, int32_t num_payloads,
-                             const void* const* payloads, const uint32_t* payload_sizes,
-                             void* keys_out, void* const* payloads_out, int64_t* indices_out,
-                             void* stream) {
-  Request R;
-  SRS_TRY(build_soa(R, row_len, key_kind, up, 0, (void*)keys, num_payloads,
-                    (void* const*)payloads, payload_sizes, keys_out, payloads_out));
-  SRS_TRY(topk_rows_validate(R, rows, row_stride, row_len, keys_out, indices_out, "sort rows"));
-  if (rows <= 0 || row_len <= 0) return SRS_OK;
-  return sort_rows_device(R, rows, row_stride, indices_out, (hipStream_t)stream);
-}
-
-int srs_sort_ragged_soa_device(int64_t num, int64_t num_segments, const int64_t* offsets,
-                               int key_kind, int up, const void* keys, int32_t num_payloads,
-                               const void* const* payloads, const uint32_t* payload_sizes,
-                               void* keys_out, void* const* payloads_out, int64_t* indices_out,
-                               void* stream) {
-  Request R;
-  SRS_TRY(build_soa(R, num, key_kind, up, 0, (void*)keys, num_payloads, (void* const*)payloads,
-                    payload_sizes, keys_out, payloads_out));
-  const bool work = num > 0 && num_segments > 0;
-  const char* shape = num_segments > (INT64_MAX >> 4) ? "num_segments + 1 overflows" : nullptr;
-  SRS_TRY(validate_outputs(R, "sort ragged", keys_out, indices_out, work ? num : 0,
-                           work ? num : 0, true, shape));
-  if (!work) return SRS_OK;
-  if (!offsets) return fail(SRS_ERR_INVALID_ARG, "offsets is NULL");
-  if ((uintptr_t)offsets % 8 != 0) return fail(SRS_ERR_INVALID_ARG, "offsets must be 8-byte aligned");
-  const size_t off_bytes = ((size_t)num_segments + 1) * sizeof(int64_t);
-  for (int o = 0; o <= R.ncols; o++) {
-    const void* op = o < R.ncols ? R.out_cols[o] : (const void*)indices_out;
-    if (op && ranges_overlap(op, (size_t)num * (o < R.ncols ? R.widths[o] : 8), offsets, off_bytes))
-      return fail(SRS_ERR_INVALID_ARG, "sort ragged outputs must not overlap the offsets");
-  }
-  return sort_ragged_device(R, num_segments, offsets, indices_out, (hipStream_t)stream);
-}
-
-int srs_topk_aos_device(int64_t num, int64_t k, int key_kind, int up, const void* elements,
-                        uint32_t elem_size, void* elements_out, int64_t* indices_out,
-                        void* stream) {
-  Request R;
-  SRS_TRY(build_aos(R, num, key_kind, up, 0, (void*)elements, elem_size, elements_out));
-  SRS_TRY(topk_validate(R, k, elements_out, indices_out));
-  if (k <= 0 || num <= 0) return SRS_OK;
-  return topk_device(R, k, indices_out, (hipStream_t)stream);
 }
 
 int srs_fill_synthetic_device(int64_t num, int key_kind, uint64_t seed, uint64_t first_index,
@@ -3827,77 +2971,6 @@ int srs_release_workspace(void) {
   }
   old.clear();  // each workspace is freed by its last holder (~Workspace)
   (void)hipGetLastError();
-  return SRS_OK;
-}
-
-int srs_debug_set_topk_candidates(int64_t max_candidates) {
-  g_topk_candidates.store(max_candidates > 0 ? max_candidates : kTopkCandidates);
-  return SRS_OK;
-}
-
-int srs_debug_last_topk(int64_t* info) {
-  if (!info) return fail(SRS_ERR_INVALID_ARG, "info is NULL");
-  Workspace* W = nullptr;
-  WsLock lk;
-  SRS_TRY(acquire_ws(&W, &lk));
-  HIP_TRY(hipDeviceSynchronize());
-  for (int i = 0; i < 3; i++) info[i] = W->topk_info[i];
-  return SRS_OK;
-}
-
-int srs_debug_set_topk_rows_route(int route) {
-  if (route < -1 || route > ROWS_LOOP) return fail(SRS_ERR_INVALID_ARG, "route must be -1, 0, 1 or 2");
-  g_topk_rows_route.store(route);
-  return SRS_OK;
-}
-
-int srs_debug_last_topk_rows(int64_t* info) {
-  if (!info) return fail(SRS_ERR_INVALID_ARG, "info is NULL");
-  Workspace* W = nullptr;
-  WsLock lk;
-  SRS_TRY(acquire_ws(&W, &lk));
-  HIP_TRY(hipDeviceSynchronize());
-  if (W->rows_pass_pending) {
-    unsigned long long passes = 0;
-    HIP_TRY(hipMemcpy(&passes, W->rowspass.p, sizeof passes, hipMemcpyDeviceToHost));
-    W->topk_rows_info[2] = (int64_t)passes;
-    W->rows_pass_pending = false;
-  }
-  for (int i = 0; i < 4; i++) info[i] = W->topk_rows_info[i];
-  return SRS_OK;
-}
-
-int64_t srs_topk_rows_max_k(void) { return kTopkRowsMaxK; }
-
-int srs_debug_set_sort_rows_route(int route) {
-  if (route < -1 || route > SORT_ROWS_LEVELS)
-    return fail(SRS_ERR_INVALID_ARG, "route must be -1, 0, 1 or 2");
-  g_sort_rows_route.store(route);
-  return SRS_OK;
-}
-
-int srs_debug_last_sort_rows(int64_t* info) {
-  if (!info) return fail(SRS_ERR_INVALID_ARG, "info is NULL");
-  Workspace* W = nullptr;
-  WsLock lk;
-  SRS_TRY(acquire_ws(&W, &lk));
-  for (int i = 0; i < 4; i++) info[i] = W->sort_rows_info[i];
-  return SRS_OK;
-}
-
-int srs_debug_set_sort_ragged_short_max(int32_t len) {
-  if (len < -1 || len > kRowsWaveMax)
-    return fail(SRS_ERR_INVALID_ARG, "short_max must be -1 (default) or 0 .. 256");
-  g_sort_ragged_short_max.store(len);
-  return SRS_OK;
-}
-
-int srs_debug_last_sort_ragged(int64_t* info) {
-  if (!info) return fail(SRS_ERR_INVALID_ARG, "info is NULL");
-  Workspace* W = nullptr;
-  WsLock lk;
-  SRS_TRY(acquire_ws(&W, &lk));
-  for (int i = 0; i < 6; i++) info[i] = W->sort_ragged_info[i];
   return SRS_OK;
 }
 

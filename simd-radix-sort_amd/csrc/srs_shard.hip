@@ -56,16 +56,10 @@
 #include <vector>
 
 #include "../../include/srs_c_api.h"
+#include "srs_driver.h"
 #include "srs_kernels.h"
 
 namespace srs {
-int set_error(int code, const std::string& msg);                                  // (srs_api.hip)
-int reserve_segments_workspace(int64_t num, int ncols, const uint32_t* widths);  // (srs_api.hip)
-// workspace frees of this thread held back while peers' messages are queued
-// on the device (a hipFree would wait for them, unbounded); srs_api.hip
-void defer_workspace_frees(bool on);
-int64_t release_deferred_frees();
-
 namespace {
 
 // ---- RCCL, resolved at first use (the library itself does not need it) ----
@@ -135,12 +129,6 @@ int nccl_rc(ncclResult_t r, const char* what) {
   return set_error(SRS_ERR_HIP, std::string(what) + " -> " + rccl().GetErrorString(r));
 }
 
-#define SH_HIP(expr)                                   \
-  do {                                                 \
-    const int r_ = hip_rc((expr), #expr);              \
-    if (r_ != SRS_OK) return r_;                       \
-  } while (0)
-
 constexpr int kBits = 12;                        // histogram bits
 constexpr int kHistBins = 1 << kBits;
 constexpr int kGroups = 512;                     // key-range groups
@@ -161,16 +149,6 @@ double timeout_s() {
   const char* e = getenv("SRS_SHARD_TIMEOUT_S");
   const double t = e && *e ? atof(e) : 600.0;
   return t > 0 ? t : 600.0;
-}
-
-int key_bytes(int kind) {
-  switch (kind) {
-    case SRS_KEY_U8: case SRS_KEY_I8: return 1;
-    case SRS_KEY_U16: case SRS_KEY_I16: return 2;
-    case SRS_KEY_U32: case SRS_KEY_I32: case SRS_KEY_F32: return 4;
-    case SRS_KEY_U64: case SRS_KEY_I64: case SRS_KEY_F64: return 8;
-    default: return 0;
-  }
 }
 
 std::string rank_list(uint64_t mask) {
@@ -354,22 +332,22 @@ struct StagedTransport : Transport {
   }
   int all_reduce_sum(uint64_t* b, size_t n, hipStream_t st) override {
     std::vector<uint64_t> v(n);
-    SH_HIP(hipMemcpyAsync(v.data(), b, n * 8, hipMemcpyDeviceToHost, st));
-    SH_HIP(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(v.data(), b, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     const int rc = exchange(v, 0);
     if (rc != SRS_OK) return rc;
-    SH_HIP(hipMemcpyAsync(b, v.data(), n * 8, hipMemcpyHostToDevice, st));
-    SH_HIP(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(b, v.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return SRS_OK;
   }
   int all_gather(const int64_t* s, int64_t* r, size_t n, hipStream_t st) override {
     std::vector<uint64_t> v(n);
-    SH_HIP(hipMemcpyAsync(v.data(), s, n * 8, hipMemcpyDeviceToHost, st));
-    SH_HIP(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(v.data(), s, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     const int rc = exchange(v, 1);
     if (rc != SRS_OK) return rc;
-    SH_HIP(hipMemcpyAsync(r, v.data(), v.size() * 8, hipMemcpyHostToDevice, st));
-    SH_HIP(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(r, v.data(), v.size() * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return SRS_OK;
   }
   int group_start() override {
@@ -392,8 +370,8 @@ struct StagedTransport : Transport {
     for (const Op& o : ops) {
       if (!o.send) continue;
       std::vector<char> m(o.bytes);
-      SH_HIP(hipMemcpyAsync(m.data(), o.buf, o.bytes, hipMemcpyDeviceToHost, o.st));
-      SH_HIP(hipStreamSynchronize(o.st));
+      HIP_TRY(hipMemcpyAsync(m.data(), o.buf, o.bytes, hipMemcpyDeviceToHost, o.st));
+      HIP_TRY(hipStreamSynchronize(o.st));
       std::lock_guard<std::mutex> lk(H.mu);
       if (H.aborted) return aborted_error();
       H.box[(size_t)me * w + o.peer].push_back(std::move(m));
@@ -418,18 +396,18 @@ struct StagedTransport : Transport {
                                              "and its receiver");
         }
       }
-      SH_HIP(hipMemcpyAsync(o.buf, m.data(), o.bytes, hipMemcpyHostToDevice, o.st));
-      SH_HIP(hipStreamSynchronize(o.st));
+      HIP_TRY(hipMemcpyAsync(o.buf, m.data(), o.bytes, hipMemcpyHostToDevice, o.st));
+      HIP_TRY(hipStreamSynchronize(o.st));
     }
     ops.clear();
     return SRS_OK;
   }
   int wait(hipStream_t st) override {
-    SH_HIP(hipStreamSynchronize(st));
+    HIP_TRY(hipStreamSynchronize(st));
     return SRS_OK;
   }
   int wait_event(hipEvent_t e) override {
-    SH_HIP(hipEventSynchronize(e));
+    HIP_TRY(hipEventSynchronize(e));
     return SRS_OK;
   }
   void abort(const std::string& w) override {
@@ -746,12 +724,12 @@ struct srs_shard_comm_s {
 namespace {
 
 int make_comm_state(srs_shard_comm c) {
-  SH_HIP(hipSetDevice(c->device));
-  SH_HIP(hipStreamCreateWithFlags(&c->cs, hipStreamNonBlocking));
-  SH_HIP(hipStreamCreateWithFlags(&c->ss, hipStreamNonBlocking));
-  SH_HIP(hipStreamCreateWithFlags(&c->own, hipStreamNonBlocking));
-  SH_HIP(hipEventCreateWithFlags(&c->ev_a, hipEventDisableTiming));
-  SH_HIP(hipEventCreateWithFlags(&c->ev_b, hipEventDisableTiming));
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamCreateWithFlags(&c->cs, hipStreamNonBlocking));
+  HIP_TRY(hipStreamCreateWithFlags(&c->ss, hipStreamNonBlocking));
+  HIP_TRY(hipStreamCreateWithFlags(&c->own, hipStreamNonBlocking));
+  HIP_TRY(hipEventCreateWithFlags(&c->ev_a, hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(&c->ev_b, hipEventDisableTiming));
   // everything the steps before the first message need, so that no rank can
   // fail there alone (the header collective is the first thing every rank does)
   int rc = c->hdr.ensure((size_t)(kHistBins + kHdr) * 8);
@@ -798,7 +776,7 @@ int shard_sort(srs_shard_comm C, int64_t n, int kind, int up, const void* keys, 
     }
   };
   if (err) np = 0;
-  const int ks = err ? 8 : key_bytes(kind);
+  const int ks = err ? 8 : key_size_of(kind);
   const int kbits = 8 * ks;
   const int CH = C->chunks > 0 ? C->chunks : (w > 1 ? kDefaultChunks : 1);
   const int R = C->rounds > 0 ? C->rounds : (w > 1 ? kDefaultRounds : kDefaultRounds1);
@@ -1091,7 +1069,7 @@ int shard_sort(srs_shard_comm C, int64_t n, int kind, int up, const void* keys, 
 int argument_error(int64_t num, int key_kind, int32_t np, const void* keys,
                    const void* const* payloads, const uint32_t* psz, void** keys_out,
                    void** payloads_out, int64_t* num_out, std::string* msg) {
-  if (!keys_out || !num_out || num < 0 || (num > 0 && !keys) || key_bytes(key_kind) == 0 ||
+  if (!keys_out || !num_out || num < 0 || (num > 0 && !keys) || key_size_of(key_kind) == 0 ||
       np < 0 || np > SRS_MAX_PAYLOADS || (np > 0 && (!payloads || !psz || !payloads_out))) {
     *msg = "srs_shard_sort_device: arguments";
     return SRS_ERR_INVALID_ARG;

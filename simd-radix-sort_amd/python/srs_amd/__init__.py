@@ -240,6 +240,54 @@ def _check_columns(keys, cols, what="tensors"):
             raise ValueError(f"{what} must all be on {keys.device} (got {t.device})")
 
 
+def _check_matrix(cols):
+    """The row-wise calls' 2-D columns, checked: (rows, row_len, stride(0))."""
+    keys = cols[0]
+    if keys.dim() != 2:
+        raise ValueError("keys must be a 2-D tensor (rows, row_len)")
+    rows, n = keys.shape
+    # (a matrix of one row or of one column may report any stride for that dim)
+    stride = keys.stride(0) if rows > 1 else max(n, 1)
+    for t in cols:
+        if not (t.is_cuda and t.dim() == 2 and tuple(t.shape) == (rows, n)):
+            raise ValueError("columns must be 2-D device tensors of equal shape")
+        if t.device != keys.device:
+            raise ValueError(f"columns must all be on {keys.device} (got {t.device})")
+        if (n > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) != stride) or stride < n:
+            raise ValueError("columns must have stride(1) == 1 and equal stride(0) >= row_len")
+    return rows, n, stride
+
+
+def _out_columns(out, cols, shape, message):
+    """`out` allocated (`shape`, one tensor per column) or given and checked:
+    at least prod(shape) elements, 1-D when shape is; else ValueError(message)."""
+    import math
+    import torch
+    dev = cols[0].device
+    if out is None:
+        return tuple(torch.empty(shape, dtype=c.dtype, device=dev) for c in cols)
+    out = tuple(out)
+    if len(out) != len(cols):
+        raise ValueError("out must hold keys_out followed by every payload_out")
+    for o, i in zip(out, cols):
+        if not (o.is_cuda and o.device == dev and o.is_contiguous() and
+                (o.dim() == 1 or len(shape) > 1) and o.numel() >= math.prod(shape) and
+                o.element_size() == i.element_size()):
+            raise ValueError(message)
+    return out
+
+
+def _soa_args(keys, payloads, out, stream, idx=False):
+    """The SoA device entry points' argument tail, from the keys pointer to
+    the stream (out None: in place; idx False: no indices_out parameter)."""
+    outs = (None, None) if out is None else (out[0].data_ptr(),
+                                             _ptr_array([o.data_ptr() for o in out[1:]]))
+    ind = () if idx is False else (None if idx is None else idx.data_ptr(),)
+    return (keys.data_ptr(), len(payloads), _ptr_array([p.data_ptr() for p in payloads]),
+            _size_array([p.element_size() for p in payloads])) + outs + ind + (
+                _stream_ptr(stream, keys.device),)
+
+
 def sort_device(keys, *payloads, up: bool = True, cmp_sort_threshold: int = 16,
                 key_kind: int | None = None, out=None, stream=None,
                 cmp_sorter: str = "insertion") -> None:
@@ -249,25 +297,17 @@ def sort_device(keys, *payloads, up: bool = True, cmp_sort_threshold: int = 16,
     GPU's current stream."""
     _check_columns(keys, (keys,) + payloads)
     kind = _torch_kind(keys) if key_kind is None else int(key_kind)
-    np_ = len(payloads)
-    pays = _ptr_array([p.data_ptr() for p in payloads])
-    sizes = _size_array([p.element_size() for p in payloads])
     if out is not None:
-        if len(out) != 1 + np_:
+        if len(out) != 1 + len(payloads):
             raise ValueError("out must hold keys_out followed by every payload_out")
         _check_columns(keys, tuple(out), "out tensors")
         for o, i in zip(out, (keys,) + payloads):
             if o.element_size() != i.element_size():
                 raise ValueError("every out tensor must have its input's element size")
-        kout = out[0].data_ptr()
-        pout = _ptr_array([o.data_ptr() for o in out[1:]])
-    else:
-        kout, pout = None, None
     with _on_device(keys):
         _check(lib().srs_sort_soa_device_leaf(keys.numel(), kind, int(bool(up)),
                                               int(cmp_sort_threshold), _leaf(cmp_sorter),
-                                              keys.data_ptr(), np_, pays, sizes, kout, pout,
-                                              _stream_ptr(stream, keys.device)))
+                                              *_soa_args(keys, payloads, out, stream)))
 
 
 def sort_segments_device(keys, *payloads, bounds, up: bool = True, key_kind: int | None = None,
@@ -322,26 +362,13 @@ def topk_device(keys, *payloads, k: int, up: bool = True, key_kind: int | None =
     kind = _torch_kind(keys) if key_kind is None else int(key_kind)
     n = keys.numel()
     kk = max(0, min(int(k), n))
-    cols = (keys,) + payloads
-    if out is None:
-        out = tuple(torch.empty(kk, dtype=c.dtype, device=keys.device) for c in cols)
-    else:
-        out = tuple(out)
-        if len(out) != len(cols):
-            raise ValueError("out must hold keys_out followed by every payload_out")
-        for o, i in zip(out, cols):
-            if not (o.is_cuda and o.device == keys.device and o.is_contiguous() and
-                    o.dim() == 1 and o.numel() >= kk and o.element_size() == i.element_size()):
-                raise ValueError("out tensors must be 1-D contiguous, on the keys' GPU, of at "
-                                 "least min(k, n) elements and of their input's element size")
+    out = _out_columns(out, (keys,) + payloads, (kk,),
+                       "out tensors must be 1-D contiguous, on the keys' GPU, of at "
+                       "least min(k, n) elements and of their input's element size")
     idx = torch.empty(kk, dtype=torch.int64, device=keys.device) if indices else None
     with _on_device(keys):
-        _check(lib().srs_topk_soa_device(
-            n, int(k), kind, int(bool(up)), keys.data_ptr(), len(payloads),
-            _ptr_array([p.data_ptr() for p in payloads]),
-            _size_array([p.element_size() for p in payloads]), out[0].data_ptr(),
-            _ptr_array([o.data_ptr() for o in out[1:]]),
-            None if idx is None else idx.data_ptr(), _stream_ptr(stream, keys.device)))
+        _check(lib().srs_topk_soa_device(n, int(k), kind, int(bool(up)),
+                                         *_soa_args(keys, payloads, out, stream, idx)))
     return out + ((idx,) if indices else ())
 
 
@@ -362,40 +389,17 @@ def topk_rows_device(keys, *payloads, k: int, up: bool = True, key_kind: int | N
     an int64 tensor of each record's position inside its row."""
     import torch
     cols = (keys,) + payloads
-    if keys.dim() != 2:
-        raise ValueError("keys must be a 2-D tensor (rows, row_len)")
-    rows, n = keys.shape
-    # (a matrix of one row or of one column may report any stride for that dim)
-    stride = keys.stride(0) if rows > 1 else max(n, 1)
-    for t in cols:
-        if not (t.is_cuda and t.dim() == 2 and tuple(t.shape) == (rows, n)):
-            raise ValueError("columns must be 2-D device tensors of equal shape")
-        if t.device != keys.device:
-            raise ValueError(f"columns must all be on {keys.device} (got {t.device})")
-        if (n > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) != stride) or stride < n:
-            raise ValueError("columns must have stride(1) == 1 and equal stride(0) >= row_len")
+    rows, n, stride = _check_matrix(cols)
     kind = _torch_kind(keys) if key_kind is None else int(key_kind)
     kk = max(0, min(int(k), n))
-    if out is None:
-        out = tuple(torch.empty((rows, kk), dtype=c.dtype, device=keys.device) for c in cols)
-    else:
-        out = tuple(out)
-        if len(out) != len(cols):
-            raise ValueError("out must hold keys_out followed by every payload_out")
-        for o, i in zip(out, cols):
-            if not (o.is_cuda and o.device == keys.device and o.is_contiguous() and
-                    o.numel() >= rows * kk and o.element_size() == i.element_size()):
-                raise ValueError("out tensors must be contiguous, on the keys' GPU, of at least "
-                                 "rows * min(k, row_len) elements and of their input's element "
-                                 "size")
+    out = _out_columns(out, cols, (rows, kk),
+                       "out tensors must be contiguous, on the keys' GPU, of at least "
+                       "rows * min(k, row_len) elements and of their input's element "
+                       "size")
     idx = torch.empty((rows, kk), dtype=torch.int64, device=keys.device) if indices else None
     with _on_device(keys):
-        _check(lib().srs_topk_rows_soa_device(
-            rows, n, stride, int(k), kind, int(bool(up)), keys.data_ptr(), len(payloads),
-            _ptr_array([p.data_ptr() for p in payloads]),
-            _size_array([p.element_size() for p in payloads]), out[0].data_ptr(),
-            _ptr_array([o.data_ptr() for o in out[1:]]),
-            None if idx is None else idx.data_ptr(), _stream_ptr(stream, keys.device)))
+        _check(lib().srs_topk_rows_soa_device(rows, n, stride, int(k), kind, int(bool(up)),
+                                              *_soa_args(keys, payloads, out, stream, idx)))
     return out + ((idx,) if indices else ())
 
 
@@ -415,40 +419,17 @@ def sort_rows_device(keys, *payloads, up: bool = True, key_kind: int | None = No
     row."""
     import torch
     cols = (keys,) + payloads
-    if keys.dim() != 2:
-        raise ValueError("keys must be a 2-D tensor (rows, row_len)")
-    rows, n = keys.shape
-    # (a matrix of one row or of one column may report any stride for that dim)
-    stride = keys.stride(0) if rows > 1 else max(n, 1)
-    for t in cols:
-        if not (t.is_cuda and t.dim() == 2 and tuple(t.shape) == (rows, n)):
-            raise ValueError("columns must be 2-D device tensors of equal shape")
-        if t.device != keys.device:
-            raise ValueError(f"columns must all be on {keys.device} (got {t.device})")
-        if (n > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) != stride) or stride < n:
-            raise ValueError("columns must have stride(1) == 1 and equal stride(0) >= row_len")
+    rows, n, stride = _check_matrix(cols)
     kind = _torch_kind(keys) if key_kind is None else int(key_kind)
-    if out is None:
-        out = tuple(torch.empty((rows, n), dtype=c.dtype, device=keys.device) for c in cols)
-    else:
-        out = tuple(out)
-        if len(out) != len(cols):
-            raise ValueError("out must hold keys_out followed by every payload_out")
-        for o, i in zip(out, cols):
-            if not (o.is_cuda and o.device == keys.device and o.is_contiguous() and
-                    o.numel() >= rows * n and o.element_size() == i.element_size()):
-                raise ValueError("out tensors must be contiguous, on the keys' GPU, of at least "
-                                 "rows * row_len elements and of their input's element size")
+    out = _out_columns(out, cols, (rows, n),
+                       "out tensors must be contiguous, on the keys' GPU, of at least "
+                       "rows * row_len elements and of their input's element size")
     idx = torch.empty((rows, n), dtype=torch.int64, device=keys.device) if indices else None
     if rows == 0 or n == 0:  # (an empty tensor has no address to pass)
         return out + ((idx,) if indices else ())
     with _on_device(keys):
-        _check(lib().srs_sort_rows_soa_device(
-            rows, n, stride, kind, int(bool(up)), keys.data_ptr(), len(payloads),
-            _ptr_array([p.data_ptr() for p in payloads]),
-            _size_array([p.element_size() for p in payloads]), out[0].data_ptr(),
-            _ptr_array([o.data_ptr() for o in out[1:]]),
-            None if idx is None else idx.data_ptr(), _stream_ptr(stream, keys.device)))
+        _check(lib().srs_sort_rows_soa_device(rows, n, stride, kind, int(bool(up)),
+                                              *_soa_args(keys, payloads, out, stream, idx)))
     return out + ((idx,) if indices else ())
 
 
@@ -488,12 +469,8 @@ def sort_ragged_device(keys, *payloads, offsets, up: bool = True, key_kind: int 
     if n == 0 or nseg <= 0:  # (an empty tensor has no address to pass)
         return out + ((idx,) if indices else ())
     with _on_device(keys):
-        _check(lib().srs_sort_ragged_soa_device(
-            n, nseg, offsets.data_ptr(), kind, int(bool(up)), keys.data_ptr(), len(payloads),
-            _ptr_array([p.data_ptr() for p in payloads]),
-            _size_array([p.element_size() for p in payloads]), out[0].data_ptr(),
-            _ptr_array([o.data_ptr() for o in out[1:]]),
-            None if idx is None else idx.data_ptr(), _stream_ptr(stream, keys.device)))
+        _check(lib().srs_sort_ragged_soa_device(n, nseg, offsets.data_ptr(), kind, int(bool(up)),
+                                                *_soa_args(keys, payloads, out, stream, idx)))
     return out + ((idx,) if indices else ())
 
 
