@@ -486,17 +486,6 @@ int srs_reset_kernel_stats(void);
 int srs_kernel_stats(const char* name, int64_t* launches, double* total_ms,
                      double* elements);
 
-/* Diagnostic builds only (-DSRS_STAMPS=1): device buffer of 64 uint64 that
- * accumulates per-phase s_memtime cycles of the scatter (slots 0..15) and
- * local (16..31) kernels; NULL disables. No effect in the product build. */
-int srs_debug_set_stamp_buffer(void* device_acc);
-
-/* Diagnostic builds only (-DSRS_DIAG_LOOKBACK): the scatter also runs a
- * decoupled look-back over its tiles and checks it against the count pass's
- * offsets. status: >= ntiles * 512 uint32 of device memory; err: 4 uint64
- * (mismatches, spin timeouts, look-back hops of digit 0). NULL disables. */
-int srs_debug_set_lookback(void* status, void* err);
-
 /* The super-group column scan: a level over one large segment
  * scans sums of 64 scan groups once it has at least min_groups groups of 32
  * tiles (default 256, i.e. 33.5 M keys; <= 0 restores it). Process-wide;

@@ -54,10 +54,6 @@ namespace srs {
 static_assert(SRS_MAX_COLS >= SRS_MAX_PAYLOADS + 1, "descriptor columns: key + payloads");
 static_assert(sizeof(SortDesc) <= 4096, "SortDesc is a kernel argument (start_kernel)");
 
-unsigned long long* g_stamp_acc = nullptr;  // srs_debug_set_stamp_buffer
-uint32_t* g_lb_status = nullptr;             // srs_debug_set_lookback
-unsigned long long* g_lb_err = nullptr;
-
 namespace {
 thread_local std::string g_err = "no error";
 // global levels run_level has run in this process: all, those on the
@@ -920,11 +916,7 @@ int run_level(Workspace* W, int ks, const SortDesc* d_desc, LevelState& S, hipSt
   // The tile-pair scatter sums its tiles' offsets from the count rows
   // itself (scatter_pair_tiles): such a level has no tile
   // offset rows and does not run tile_offs_kernel.
-#ifdef SRS_DIAG_LOOKBACK
-  const bool row_offs = false;  // (the look-back is checked against the rows)
-#else
   const bool row_offs = pairs && offs32 && S.row_offs;
-#endif
   g_level_counts[0]++;
   g_level_counts[1] += pairs;
   g_level_counts[2] += row_offs;
@@ -960,8 +952,6 @@ int run_level(Workspace* W, int ks, const SortDesc* d_desc, LevelState& S, hipSt
                    (Seg*)W->local2.p, (Seg*)W->copy.p, d_ctr, lut_rbits, st, (int)M.stripe,
                    (uint32_t*)W->prun.p, !row_offs);
   }
-  if (g_lb_status)  // (diagnostic look-back: fresh status words per level)
-    HIP_TRY(hipMemsetAsync(g_lb_status, 0, (size_t)ntiles * kMaxBins * 4, st));
   {
     TimedScope ts("scatter", (double)0, st, lv);
     if (row_offs)
@@ -1096,9 +1086,6 @@ int list_begin(Workspace* W, const Request& Q, bool inplace, bool levels, hipStr
   if (levels) SRS_TRY(ensure(W->tmp, tmp_bytes, ws_alloc_mode(), true));
   set_columns(Q, *d, levels ? (char*)W->tmp.p : nullptr, nullptr, false, 0, tmp_off.data(),
               inplace);
-  d->stamp_acc = g_stamp_acc;
-  d->lb_status = g_lb_status;
-  d->lb_err = g_lb_err;
   SRS_TRY(ensure(W->desc, sizeof(SortDesc)));
   *d_desc = (SortDesc*)W->desc.p;
   launch_set_desc(*d, *d_desc, st);
@@ -1152,7 +1139,6 @@ int run_small(Workspace* W, const Request& R, hipStream_t st) {
   d.leaf_skip = leaf_skip_of(R);
   const int ksl = ks | (d.canon_zero ? SRS_KS_CANON : 0);
   set_columns(R, d, nullptr, nullptr, false, 0, nullptr, inplace);
-  d.stamp_acc = g_stamp_acc;
   const Seg g{0, n, d.key_bits, inplace ? BUF_OUT : BUF_IN};
   DevBuf* tk = nullptr;
   SRS_TRY(taken_slot(W, st, &tk));
@@ -1675,9 +1661,6 @@ int run_sort(Workspace* W, const Request& R, hipStream_t st) {
   d.tmp2 = L.tmp2;
   set_columns(R, d, (char*)W->tmp.p, L.tmp2 ? (char*)W->tmp2.p : nullptr, L.aos_cols,
               L.slice_bytes, L.tmp_off.data(), inplace, L.pair_cols);
-  d.stamp_acc = g_stamp_acc;
-  d.lb_status = g_lb_status;
-  d.lb_err = g_lb_err;
 
   // ---- the first level's plan (key sample: digit table, ranges, stripes) ----
   FirstLevel F;
@@ -2789,19 +2772,6 @@ int srs_kernel_stats(const char* name, int64_t* launches, double* total_ms, doub
   if (launches) *launches = k.launches;
   if (total_ms) *total_ms = k.ms;
   if (elements) *elements = k.elems;
-  return SRS_OK;
-}
-
-int srs_debug_set_stamp_buffer(void* device_acc) {
-  g_stamp_acc = (unsigned long long*)device_acc;
-  return SRS_OK;
-}
-
-// (diagnostic builds, SRS_DIAG_LOOKBACK: status words of at least ntiles * 512
-// u32, zeroed by the caller before every level, and 4 u64 error counters)
-int srs_debug_set_lookback(void* status, void* err) {
-  g_lb_status = (uint32_t*)status;
-  g_lb_err = (unsigned long long*)err;
   return SRS_OK;
 }
 

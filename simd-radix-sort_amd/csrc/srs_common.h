@@ -70,11 +70,6 @@ struct SortDesc {
   // consecutive aligned blocks of 2^lut_shift key values
   uint64_t rng_hi[4];
   uint32_t rng_adj[4];
-  unsigned long long* stamp_acc;  // diagnostic builds only (SRS_STAMPS)
-  // diagnostic builds only (SRS_DIAG_LOOKBACK): per (tile, digit) look-back
-  // status words of the scatter and error counters [mismatch, timeout, hops]
-  uint32_t* lb_status;
-  unsigned long long* lb_err;
 };
 
 struct Seg {
@@ -112,10 +107,7 @@ struct GTile {
 };
 // average piece (one stripe's share of one bucket) for uniform keys: 95 % of
 // a tile, so a piece almost never spills a second, nearly empty tile
-#ifndef SRS_STRIPE_KPB
-#define SRS_STRIPE_KPB 3904
-#endif
-constexpr int kStripeKeysPerBucket = SRS_STRIPE_KPB;
+constexpr int kStripeKeysPerBucket = 3904;
 
 // The mid-size launch's answer to the host (coherent pinned host memory):
 // written by workgroup 0 once the first level's bucket sizes are known, so
@@ -148,44 +140,20 @@ struct ListCounters {
 };
 
 // Tuning constants (see DESIGN.md §4 for how they were chosen).
-// (overridable at build time for tuning sweeps: tools/build_variants.sh)
-#ifndef SRS_SCATTER_THREADS
-#define SRS_SCATTER_THREADS 1024
-#endif
-#ifndef SRS_SCATTER_ITEMS
-#define SRS_SCATTER_ITEMS 4
-#endif
-#ifndef SRS_SCATTER_WAVES_PER_EU
-#define SRS_SCATTER_WAVES_PER_EU 8
-#endif
-#ifndef SRS_SCATTER_SDIG
-#define SRS_SCATTER_SDIG 1   // stage each slot's digit (0: recompute it from the key)
-#endif
-#ifndef SRS_LOCAL_RANK_SPLIT
-#define SRS_LOCAL_RANK_SPLIT 2
-#endif
-constexpr int kScatterThreads = SRS_SCATTER_THREADS;
-constexpr int kScatterItems = SRS_SCATTER_ITEMS;
+constexpr int kScatterThreads = 1024;
+constexpr int kScatterItems = 4;
+constexpr int kScatterWavesPerEU = 8;
 constexpr int kTile = kScatterThreads * kScatterItems;   // keys per tile
-#ifndef SRS_COUNT_THREADS
-#define SRS_COUNT_THREADS 256
-#endif
-constexpr int kCountThreads = SRS_COUNT_THREADS;         // count kernel: one tile per block
+constexpr int kCountThreads = 256;                       // count kernel: one tile per block
 constexpr int kCountItems = kTile / kCountThreads;
 static_assert(kCountItems * kCountThreads == kTile, "count block shape");
-#ifndef SRS_MAX_DIGIT_BITS
-#define SRS_MAX_DIGIT_BITS 9
-#endif
-constexpr int kMaxDigitBits = SRS_MAX_DIGIT_BITS;
+constexpr int kMaxDigitBits = 9;
 // launch_* key_size flag: the canon-zero float case (SortDesc::canon_zero),
 // selects the kernel instantiations that map -0.0 to +0.0
 #define SRS_KS_CANON 0x100
 constexpr int kMaxBins = 1 << kMaxDigitBits;   // histogram row stride (tile-major)
 static_assert(kScatterThreads >= kMaxBins, "the scatter tile scan gives one bin per thread");
-#ifndef SRS_SCAN_GROUP
-#define SRS_SCAN_GROUP 32
-#endif
-constexpr int kScanGroup = SRS_SCAN_GROUP;      // tiles per column-scan group
+constexpr int kScanGroup = 32;                  // tiles per column-scan group
 constexpr int kHistMaxBits = 12;                // srs_key_histogram_device
 constexpr int kMaxRanges = 4;                   // key clusters of a range level (lut_mode 2)
 constexpr int kLdsLutBits = 12;                 // flat digit tables up to 4096 entries live in LDS
@@ -201,63 +169,30 @@ static_assert((kSampleMaxChunks + kSampleWGs - 1) / kSampleWGs * kSampleChunk < 
 // local sort classes: fast kernel (atomic bucket pass + rank) in two sizes,
 // then the stable kernel and the LSD kernel as fallbacks (same capacity as
 // the large class)
-#ifndef SRS_LOCAL_THREADS
-#define SRS_LOCAL_THREADS 1024
-#endif
-#ifndef SRS_LOCAL_ITEMS
-#define SRS_LOCAL_ITEMS 8
-#endif
-constexpr int kLocalItems = SRS_LOCAL_ITEMS;
-constexpr int kLocalThreads = SRS_LOCAL_THREADS;
+constexpr int kLocalItems = 8;
+constexpr int kLocalThreads = 1024;
 constexpr int kLocalCap = kLocalThreads * kLocalItems;    // 8192 keys per segment
-#ifndef SRS_LOCAL_SMALL_THREADS
-#define SRS_LOCAL_SMALL_THREADS 512
-#endif
-#ifndef SRS_LOCAL_SMALL_WGS_PER_CU
-#define SRS_LOCAL_SMALL_WGS_PER_CU 3
-#endif
-constexpr int kLocalThreadsSmall = SRS_LOCAL_SMALL_THREADS;
+constexpr int kLocalRankSplit = 2;  // the rank step takes a thread's slots in this many parts
+constexpr int kLocalThreadsSmall = 512;
 constexpr int kLocalItemsSmall = 4096 / kLocalThreadsSmall;
 constexpr int kLocalCapSmall = kLocalThreadsSmall * kLocalItemsSmall;  // 4096
 // occupancy the LDS footprint allows (90 KB -> 1 block/CU; 49 KB -> 3 blocks/CU)
 constexpr int kLocalWavesPerEU = kLocalThreads / 64 / 4;
-constexpr int kLocalWavesPerEUSmall = SRS_LOCAL_SMALL_WGS_PER_CU * kLocalThreadsSmall / 64 / 4;
+constexpr int kLocalWavesPerEUSmall = 3 * kLocalThreadsSmall / 64 / 4;
 // direct local kernel (small class, common SoA shape): 4 workgroups of
 // 256 x 16 per CU
 constexpr int kLocalDirectThreads = 256;
 constexpr int kLocalDirectItems = 4096 / kLocalDirectThreads;
-#ifndef SRS_LOCAL_DIRECT_WGS_PER_CU
-#define SRS_LOCAL_DIRECT_WGS_PER_CU 4
-#endif
-constexpr int kLocalDirectWavesPerEU = SRS_LOCAL_DIRECT_WGS_PER_CU * kLocalDirectThreads / 64 / 4;
+constexpr int kLocalDirectWavesPerEU = 4 * kLocalDirectThreads / 64 / 4;
 // and its large class (up to kLocalCap records): 2 workgroups of 512 x 16 per CU
 constexpr int kLocalDirectThreads2 = 512;
 constexpr int kLocalDirectItems2 = 8192 / kLocalDirectThreads2;
 constexpr int kLocalDirectWavesPerEU2 = 2 * kLocalDirectThreads2 / 64 / 4;
-// cache-policy bits of the scatter's / the direct local kernel's column
-// loads (buffer-load aux operand; 0 = default)
-#ifndef SRS_SCATTER_LOAD_AUX
-#define SRS_SCATTER_LOAD_AUX 0
-#endif
-#ifndef SRS_LOCAL_LOAD_AUX
-#define SRS_LOCAL_LOAD_AUX 0
-#endif
-// direct local kernel: bucket digit = the sort word's top bits (1; measured
-// slower for C2: local 4.62-4.65 -> 6.02-6.07 ms), or the
-// key's top varying bits with a ballot-ranked exact pass in the pair mode (0)
-#ifndef SRS_DIRECT_WORD_DIGIT
-#define SRS_DIRECT_WORD_DIGIT 0
-#endif
-#ifndef SRS_DIRECT_RANK_SPLIT
-#define SRS_DIRECT_RANK_SPLIT 2
-#endif
-#ifndef SRS_DIRECT_EARLY_PAYLOAD
-#define SRS_DIRECT_EARLY_PAYLOAD 0
-#endif
-#ifndef SRS_LOCAL_STABLE_ITEMS
-#define SRS_LOCAL_STABLE_ITEMS 8
-#endif
-constexpr int kLocalStableItems = SRS_LOCAL_STABLE_ITEMS;
+// (its bucket digit is the key's top varying bits, with a ballot-ranked exact
+// pass in the pair mode; the sort word's top bits measured slower for C2:
+// local 4.62-4.65 -> 6.02-6.07 ms)
+constexpr int kDirectRankSplit = 2;  // parts of the direct kernels' rank step
+constexpr int kLocalStableItems = 8;
 constexpr int kLocalStableThreads = kLocalCap / kLocalStableItems;
 constexpr int kLocalStableThreadsSmall = kLocalCapSmall / kLocalStableItems;
 static_assert(kLocalStableThreads * kLocalStableItems == kLocalCap, "fallback capacity");
@@ -266,10 +201,7 @@ constexpr int kLocalTarget = 6144;                        // digit sizing target
 // average bucket that still lands in the small class: ~94 % full for uniform
 // keys (the small class is 2.5x cheaper per key than the large one, and a
 // half-empty small segment costs ~1.5x per key of a full one)
-#ifndef SRS_LOCAL_SMALL_TARGET
-#define SRS_LOCAL_SMALL_TARGET 3840
-#endif
-constexpr int kLocalSmallTarget = SRS_LOCAL_SMALL_TARGET;
+constexpr int kLocalSmallTarget = 3840;
 
 // Digit width for a segment of `len` keys with `rbits` unsorted bits: as many
 // bits as needed to bring buckets under kLocalTarget, spread evenly over the

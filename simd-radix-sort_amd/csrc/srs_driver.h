@@ -34,9 +34,6 @@ int fail(int code, const std::string& msg);  // sets srs_last_error; returns cod
 
 int64_t knob_int(const char* name, int64_t dflt);
 int ws_alloc_mode();  // SRS_WS_ALLOC: how the big workspace buffers are backed
-extern unsigned long long* g_stamp_acc;  // srs_debug_set_stamp_buffer
-extern uint32_t* g_lb_status;            // srs_debug_set_lookback
-extern unsigned long long* g_lb_err;
 
 // kernel timing (optional; HIP events around every launch on its stream)
 struct TimingRec {

@@ -43,11 +43,7 @@ __device__ __forceinline__ T gld(const void* p) {
 }
 template <typename T>
 __device__ __forceinline__ void gst(void* p, T v) {
-#if SRS_DIAG_NT_STORES  // (diagnostic: nontemporal element stores)
-  __builtin_nontemporal_store(v, (SRS_GLOBAL T*)(p));
-#else
   *(SRS_GLOBAL T*)(p) = v;
-#endif
 }
 
 __device__ __forceinline__ uint64_t load_w(const char* p, uint32_t w) {
@@ -135,15 +131,14 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t strip_rsrc(const char* base, u
                                            0x00020000);
 }
 
-// voff: per-lane byte offset; soff: wave-uniform byte offset (an SGPR);
-// AUX: the cache-policy bits of the load (0: default)
-template <int W, int AUX = 0>
+// voff: per-lane byte offset; soff: wave-uniform byte offset (an SGPR)
+template <int W>
 __device__ __forceinline__ uint64_t bld(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff = 0) {
-  if constexpr (W == 1) return __builtin_amdgcn_raw_buffer_load_b8(r, voff, soff, AUX);
-  else if constexpr (W == 2) return __builtin_amdgcn_raw_buffer_load_b16(r, voff, soff, AUX);
-  else if constexpr (W == 4) return __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, AUX);
+  if constexpr (W == 1) return __builtin_amdgcn_raw_buffer_load_b8(r, voff, soff, 0);
+  else if constexpr (W == 2) return __builtin_amdgcn_raw_buffer_load_b16(r, voff, soff, 0);
+  else if constexpr (W == 4) return __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0);
   else {
-    const auto v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, AUX);
+    const auto v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
     return (uint64_t)v[0] | ((uint64_t)v[1] << 32);
   }
 }
@@ -154,7 +149,7 @@ __device__ __forceinline__ uint64_t bld(__amdgpu_buffer_rsrc_t r, uint32_t voff,
 // and a tile's loads stay in flight together (guarded flat loads of 1/2/4-byte
 // columns were each followed by a full vmcnt(0) wait inside loops; C2
 // 29.9 -> 26.0 ms on the same box). Slots past cnt read 0.
-template <int IT, bool DENSE = false, int FW = 0, int AUX = 0>
+template <int IT, bool DENSE = false, int FW = 0>
 __device__ __forceinline__ void load_strip(uint64_t (&dst)[IT], const char* src, uint32_t w,
                                            uint32_t st, int64_t first, int ebase, int cnt) {
   const __amdgpu_buffer_rsrc_t r =
@@ -167,8 +162,8 @@ __device__ __forceinline__ void load_strip(uint64_t (&dst)[IT], const char* src,
     // (a per-slot VGPR offset would be hoisted and held live)
 #pragma unroll
     for (int k = 0; k < IT; k++) {
-      if constexpr (D) dst[k] = bld<W, AUX>(r, o0 + (uint32_t)k * 64u * W);
-      else dst[k] = bld<W, AUX>(r, o0, __builtin_amdgcn_readfirstlane((uint32_t)k * 64u * st));
+      if constexpr (D) dst[k] = bld<W>(r, o0 + (uint32_t)k * 64u * W);
+      else dst[k] = bld<W>(r, o0, __builtin_amdgcn_readfirstlane((uint32_t)k * 64u * st));
     }
   });
 }
@@ -336,36 +331,6 @@ __device__ __forceinline__ T block_excl_scan(T v, T* sh, T* total) {
   __syncthreads();
   return r;
 }
-
-// ---- diagnostic phase stamps (build with -DSRS_STAMPS=1; never in the product
-// build). Wave 0 drains its memory counters and reads s_memtime at each phase
-// boundary; per-phase cycles are summed over workgroups into
-// desc->stamp_acc[kernel * 16 + phase] (slot 0 counts workgroups).
-#ifndef SRS_STAMPS
-#define SRS_STAMPS 0
-#endif
-#if SRS_STAMPS
-#define STAMP_DECL unsigned long long ts_[16] = {0}; int tsn_ = 0;
-#define STAMP()                                                              \
-  do {                                                                       \
-    if (threadIdx.x == 0) {                                                  \
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");            \
-      if (tsn_ < 16) ts_[tsn_++] = __builtin_amdgcn_s_memtime();              \
-    }                                                                        \
-  } while (0)
-#define STAMP_FLUSH(kid)                                                     \
-  do {                                                                       \
-    if (threadIdx.x == 0 && desc->stamp_acc) {                               \
-      atomicAdd(&desc->stamp_acc[(kid) * 16], 1ull);                         \
-      for (int i_ = 1; i_ < tsn_; i_++)                                      \
-        atomicAdd(&desc->stamp_acc[(kid) * 16 + i_], ts_[i_] - ts_[i_ - 1]); \
-    }                                                                        \
-  } while (0)
-#else
-#define STAMP_DECL
-#define STAMP() do {} while (0)
-#define STAMP_FLUSH(kid) do {} while (0)
-#endif
 
 // Workgroup barrier that orders LDS accesses only. __syncthreads() also waits
 // for every outstanding global load AND store of the wave (s_waitcnt
@@ -773,14 +738,6 @@ __device__ __forceinline__ DigitLut stage_lut(const SortDesc* desc, uint16_t* sl
 // ---------------------------------------------------------------------------
 // count: per-tile digit histogram (one tile-major row per tile) + varying bits
 // ---------------------------------------------------------------------------
-// A workgroup counts kCountTiles consecutive tiles; the next tile's loads go
-// out before the current one is counted (two register sets, LDS-only
-// barriers), so a workgroup's reads stay in flight across its tiles.
-#ifndef SRS_COUNT_TILES
-#define SRS_COUNT_TILES 1
-#endif
-constexpr int kCountTiles = SRS_COUNT_TILES;
-
 struct CountTile {
   int64_t t;     // tile index (its histogram row)
   int32_t s;     // segment
@@ -941,8 +898,9 @@ __device__ __forceinline__ void count_add(const SortDesc* __restrict__ desc,
 }
 
 // After a barrier: the tile's row of u16 counts (a tile holds <= kTile = 4096
-// keys; one coalesced 2*nb-byte write, packed pairs), h zeroed again for the
-// tile after next, the varying bits published.
+// keys; one coalesced 2*nb-byte write, packed pairs), the varying bits
+// published. (h and sor are reset as for a further tile; there is none, but
+// without those stores the kernel compiles to other code.)
 __device__ __forceinline__ void count_flush(const SegPlan* __restrict__ plan, const CountTile& T,
                                             uint32_t* h, unsigned long long* sor,
                                             uint16_t* __restrict__ hist,
@@ -984,37 +942,29 @@ __global__ __launch_bounds__(kCountThreads, (kCountMinWaves<LUT, (int)sizeof(KT)
     const int32_t* __restrict__ tile_seg, uint16_t* __restrict__ hist,
     unsigned long long* __restrict__ var_or, unsigned long long* __restrict__ var_and,
     const GTile* __restrict__ gt, int64_t ntiles, const int32_t* __restrict__ torder) {
-  constexpr int NH = kCountTiles > 1 ? 2 : 1;  // (one row when nothing is prefetched:
-  __shared__ uint32_t h[NH][kMaxBins + 16];     //  the LUT pass keeps 6 workgroups per CU;
-                                                //  bin kMaxBins: keys past the tile's end)
-  __shared__ unsigned long long sh_or[NH][2];  // the tile's key OR and AND
-  int64_t t0 = xcd_remap(blockIdx.x, gridDim.x) * kCountTiles;
+  __shared__ uint32_t h[kMaxBins + 16];  // (one row: the LUT pass keeps 6 workgroups per CU;
+                                         //  bin kMaxBins: keys past the tile's end)
+  __shared__ unsigned long long sh_or[2];  // the tile's key OR and AND
+  int64_t t0 = xcd_remap(blockIdx.x, gridDim.x);
   // gathered level: tiles in stripe order (each stripe's pieces lie back to
   // back, so the reads sweep memory); the rows do not depend on the order
-  if (torder && kCountTiles == 1) t0 = torder[t0];
+  if (torder) t0 = torder[t0];
   __shared__ alignas(16) uint16_t slut[kLutLdsEntries<LUT>];
-  U ra[kCountItems], rb[kCountItems];
-  CountTile A = count_load<KT, U>(desc, plan, tile_seg, gt, t0, ntiles, ra);
+  U ra[kCountItems];
+  const CountTile A = count_load<KT, U>(desc, plan, tile_seg, gt, t0, ntiles, ra);
   const DigitLut lut = stage_lut<LUT, kCountThreads>(desc, slut);
-  for (uint32_t i = threadIdx.x; i < NH * (kMaxBins + 16); i += kCountThreads) (&h[0][0])[i] = 0;
-  if (threadIdx.x < NH) {
-    sh_or[threadIdx.x][0] = 0;
-    sh_or[threadIdx.x][1] = ~0ull;
+  for (uint32_t i = threadIdx.x; i < kMaxBins + 16; i += kCountThreads) h[i] = 0;
+  if (threadIdx.x == 0) {
+    sh_or[0] = 0;
+    sh_or[1] = ~0ull;
   }
   lds_barrier();
-#pragma unroll
-  for (int i = 0; i < kCountTiles; i += 2) {
-    CountTile B;
-    if (i + 1 < kCountTiles) B = count_load<KT, U>(desc, plan, tile_seg, gt, t0 + i + 1, ntiles, rb);
-    count_add<KT, U, LUT, CZ>(desc, plan, A, ra, h[0], &sh_or[0][0], lut);
+  // (one trip; written without the loop, the same statements compile to other,
+  // longer code in every instantiation, which nobody has timed)
+  for (int i = 0; i < 1; i++) {
+    count_add<KT, U, LUT, CZ>(desc, plan, A, ra, h, sh_or, lut);
     lds_barrier();
-    count_flush(plan, A, h[0], &sh_or[0][0], hist, var_or, var_and);
-    if (i + 1 < kCountTiles) {
-      if (i + 2 < kCountTiles) A = count_load<KT, U>(desc, plan, tile_seg, gt, t0 + i + 2, ntiles, ra);
-      count_add<KT, U, LUT, CZ>(desc, plan, B, rb, h[NH - 1], &sh_or[NH - 1][0], lut);
-      lds_barrier();
-      count_flush(plan, B, h[NH - 1], &sh_or[NH - 1][0], hist, var_or, var_and);
-    }
+    count_flush(plan, A, h, sh_or, hist, var_or, var_and);
   }
 }
 
@@ -1435,7 +1385,7 @@ struct ScatterLds {
   uint64_t sval[kTile];
   // digit of each staged slot (big-table passes recompute it instead: their 24 KB
   // table must leave room for two workgroups per CU)
-  uint16_t sdig[(LUT == 1 || !SRS_SCATTER_SDIG) ? 1 : kTile];
+  uint16_t sdig[LUT == 1 ? 1 : kTile];
   alignas(8) uint16_t wc[kScatterThreads / 64][kMaxBins];  // zeroed as u64
   uint16_t bin_start[kMaxBins];  // tile offsets <= kTile fit 16 bits
   int64_t gdst[kMaxBins];
@@ -1446,58 +1396,7 @@ struct TileInfo {
   int64_t base;   // first element of the tile
   int32_t cnt;    // elements in the tile (0: skip)
   int32_t s;      // segment
-  int64_t t;      // tile index in the level
 };
-
-#ifdef SRS_DIAG_LOOKBACK
-// Diagnostic: a decoupled look-back over the tiles of a
-// segment, per digit, as a one-pass scatter would need it instead of the
-// count pass + scans: publish the tile's digit count (flag 1), walk back
-// over the predecessors' words (flag 1: add and continue, flag 2: an
-// inclusive prefix, add and stop), publish the inclusive prefix (flag 2).
-// Status words are single 4-byte sc1 stores / sc1 loads (self-contained
-// {flag, value} granules). The result is only compared with the offsets
-// the count pass produced (lb_err[0] counts mismatches); spins are bounded.
-__device__ __forceinline__ void diag_lookback(const SortDesc* __restrict__ desc,
-                                              const SegPlan& P, int64_t t, uint32_t d,
-                                              uint32_t tb, int64_t my_off,
-                                              const uint64_t* __restrict__ offs,
-                                              const uint32_t* __restrict__ offs32) {
-  uint32_t* st = desc->lb_status;
-  const uint64_t first = offs32 ? offs32[P.tile_base * kMaxBins + d] : offs[P.tile_base * kMaxBins + d];
-  uint32_t pre = 0;
-  if (t == P.tile_base) {
-    __hip_atomic_store(&st[t * kMaxBins + d], (2u << 30) | tb, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-  } else {
-    __hip_atomic_store(&st[t * kMaxBins + d], (1u << 30) | tb, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-    int64_t j = t - 1;
-    uint32_t spins = 0, hops = 0;
-    while (true) {
-      const uint32_t v = __hip_atomic_load(&st[j * kMaxBins + d], __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_AGENT);
-      const uint32_t f = v >> 30;
-      if (f == 0) {
-        if (++spins > (1u << 22)) {
-          atomicAdd(&desc->lb_err[1], 1ull);
-          break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-        continue;
-      }
-      pre += v & 0x3FFFFFFFu;
-      hops++;
-      if (f == 2 || j == P.tile_base) break;
-      j--;
-    }
-    __hip_atomic_store(&st[t * kMaxBins + d], (2u << 30) | (pre + tb), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-    if (d == 0) atomicAdd(&desc->lb_err[2], (unsigned long long)hops);
-  }
-  if ((uint64_t)my_off - first != pre) atomicAdd(&desc->lb_err[0], 1ull);
-}
-#endif
 
 template <typename KT, typename U, bool PRE3>
 __device__ __forceinline__ TileInfo scatter_load_tile(
@@ -1508,7 +1407,6 @@ __device__ __forceinline__ TileInfo scatter_load_tile(
     uint64_t (&v2)[kScatterItems], int64_t& my_off) {
   constexpr int IT = kScatterItems;
   TileInfo ti;
-  ti.t = t;
   ti.s = tile_seg[t];
   const SegPlan P = plan[ti.s];
   if (gt) {  // gathered level (never skipped)
@@ -1521,18 +1419,17 @@ __device__ __forceinline__ TileInfo scatter_load_tile(
     ti.cnt = P.skip ? 0 : (rem < kTile ? (int)rem : kTile);
   }
   const int ebase = (int)(threadIdx.x >> 6) * IT * 64 + (int)lane_id();
-  constexpr int LA = SRS_SCATTER_LOAD_AUX;
-  load_strip<IT, false, 0, LA>(v0, desc->cols[0].base[P.buf], desc->cols[0].width,
-                               desc->cols[0].stride[P.buf], ti.base, ebase, ti.cnt);
+  load_strip<IT>(v0, desc->cols[0].base[P.buf], desc->cols[0].width,
+                 desc->cols[0].stride[P.buf], ti.base, ebase, ti.cnt);
   // (desc->pair: in TMP / TMP2 columns 1 and 2 are one 8-byte word column,
   // loaded whole into v1)
   const bool pair_src = PRE3 && desc->pair && (P.buf == BUF_TMP || P.buf == BUF_TMP2);
   if (ncols > 1)
-    load_strip<IT, false, 0, LA>(v1, desc->cols[1].base[P.buf], pair_src ? 8u : desc->cols[1].width,
-                                 desc->cols[1].stride[P.buf], ti.base, ebase, ti.cnt);
+    load_strip<IT>(v1, desc->cols[1].base[P.buf], pair_src ? 8u : desc->cols[1].width,
+                   desc->cols[1].stride[P.buf], ti.base, ebase, ti.cnt);
   if (PRE3 && ncols > 2 && !pair_src)
-    load_strip<IT, false, 0, LA>(v2, desc->cols[2].base[P.buf], desc->cols[2].width,
-                                 desc->cols[2].stride[P.buf], ti.base, ebase, ti.cnt);
+    load_strip<IT>(v2, desc->cols[2].base[P.buf], desc->cols[2].width,
+                   desc->cols[2].stride[P.buf], ti.base, ebase, ti.cnt);
   my_off = 0;
   if (ti.cnt > 0 && threadIdx.x < (1u << P.bits))
     my_off = offs32 ? (int64_t)offs32[t * kMaxBins + threadIdx.x]
@@ -1545,8 +1442,7 @@ __device__ __forceinline__ void scatter_process_tile(
     const SortDesc* __restrict__ desc, const SegPlan* __restrict__ plan, ScatterLds<LUT>& L,
     const TileInfo& ti, int ncols, const uint64_t (&v0)[kScatterItems],
     uint64_t (&v1)[kScatterItems], uint64_t (&v2)[kScatterItems], int64_t my_off,
-    const DigitLut& lut, const uint64_t* __restrict__ lb_offs = nullptr,
-    const uint32_t* __restrict__ lb_offs32 = nullptr) {
+    const DigitLut& lut) {
   constexpr int NT = kScatterThreads;
   constexpr int IT = kScatterItems;
   constexpr int NW = NT / 64;
@@ -1560,8 +1456,6 @@ __device__ __forceinline__ void scatter_process_tile(
   xf.init(*desc);
   const int kbytes = desc->key_bits >> 3;
   const uint64_t kmask = kbytes == 8 ? ~0ull : ((1ull << (8 * kbytes)) - 1);
-  STAMP_DECL
-  STAMP();
 
   if constexpr (LUT) lds_barrier();  // publishes the staged digit table
   // each wave zeroes its own counter row (no barrier: a wave's LDS accesses
@@ -1576,7 +1470,6 @@ __device__ __forceinline__ void scatter_process_tile(
   uint32_t dg[IT];
 #pragma unroll
   for (int k = 0; k < IT; k++) dg[k] = pass_digit<LUT>(xf((U)(v0[k] & kmask)), P.shift, mask, lut);
-  STAMP();  // 1: loads returned
 
   uint32_t pos[IT];
   // digits are < 2^kMaxDigitBits: every ballot unconditionally (no per-bit
@@ -1584,7 +1477,6 @@ __device__ __forceinline__ void scatter_process_tile(
   wlms_rank_fn<IT, kMaxDigitBits, true>([&](int k) { return dg[k]; }, valid, P.bits,
                                         &L.wc[wave][0], pos);
   lds_barrier();
-  STAMP();  // 2: ranked
 
   {  // per-bin totals over waves -> per-wave exclusive offsets; tile scan
     const uint32_t my_bin = threadIdx.x;
@@ -1602,13 +1494,8 @@ __device__ __forceinline__ void scatter_process_tile(
       L.bin_start[my_bin] = ex;
       L.gdst[my_bin] = P.start + my_off - (int64_t)ex;
     }
-#ifdef SRS_DIAG_LOOKBACK
-    if (my_bin < nb && desc->lb_status)
-      diag_lookback(desc, P, ti.t, my_bin, tb, my_off, lb_offs, lb_offs32);
-#endif
   }
   lds_barrier();
-  STAMP();  // 3: tile scan
 
 #pragma unroll
   for (int k = 0; k < IT; k++) {
@@ -1616,26 +1503,11 @@ __device__ __forceinline__ void scatter_process_tile(
       const uint32_t d = dg[k];
       pos[k] = L.bin_start[d] + L.wc[wave][d] + pos[k];
       L.sval[pos[k]] = v0[k];
-      if constexpr (LUT != 1 && SRS_SCATTER_SDIG) L.sdig[pos[k]] = (uint16_t)d;
+      if constexpr (LUT != 1) L.sdig[pos[k]] = (uint16_t)d;
     }
   }
   lds_barrier();
-  STAMP();  // 4: column 0 staged
 
-#ifdef SRS_DIAG_WIN
-  // diagnostic (wrong result): each window of SRS_DIAG_WIN consecutive tiles
-  // of a segment is its own little bucket array, so the scattered runs land
-  // in a window of SRS_DIAG_WIN * kTile records instead of the whole segment
-  auto diag_win = [&](int j, uint32_t d) -> int64_t {
-    constexpr int S = SRS_DIAG_WIN;
-    const int64_t tl = (ti.base - P.start) / kTile;
-    const int64_t wb = P.start + (tl / S) * S * kTile;
-    const int64_t per = (int64_t)S * kTile >> P.bits;
-    const int64_t r = ((tl % S) * (per / S) + (j - (int)L.bin_start[d])) % per;
-    const int64_t a = wb + (int64_t)d * per + r;
-    return a < P.start + P.len ? a : ti.base + j;
-  };
-#endif
   // column 0: output slot j's bucket was staged with it
   uint16_t dout[IT];
   {
@@ -1649,16 +1521,10 @@ __device__ __forceinline__ void scatter_process_tile(
         if (j < cnt) {
           const uint64_t x = L.sval[j];
           uint32_t d;
-          if constexpr (LUT == 1 || !SRS_SCATTER_SDIG) d = pass_digit<LUT>(xf((U)(x & kmask)), P.shift, mask, lut);
+          if constexpr (LUT == 1) d = pass_digit<LUT>(xf((U)(x & kmask)), P.shift, mask, lut);
           else d = L.sdig[j];
           dout[i] = (uint16_t)d;
-          #ifdef SRS_DIAG_SEQW
-          stw<decltype(W_)::value>(out + ((int64_t)j + ti.base) * (int64_t)st, x);
-#elif defined(SRS_DIAG_WIN)
-          stw<decltype(W_)::value>(out + diag_win(j, d) * (int64_t)st, x);
-#else
           stw<decltype(W_)::value>(out + ((int64_t)j + L.gdst[d]) * (int64_t)st, x);
-#endif
         }
       }
     });
@@ -1682,23 +1548,16 @@ __device__ __forceinline__ void scatter_process_tile(
       if (valid(k)) L.sval[pos[k]] = v[k];
     lds_barrier();
     if (c + STEP < ncols)
-      load_strip<IT, false, 0, SRS_SCATTER_LOAD_AUX>(
-          v, desc->cols[c + STEP].base[P.buf], desc->cols[c + STEP].width,
-          desc->cols[c + STEP].stride[P.buf], ti.base, ebase, cnt);
+      load_strip<IT>(v, desc->cols[c + STEP].base[P.buf], desc->cols[c + STEP].width,
+                     desc->cols[c + STEP].stride[P.buf], ti.base, ebase, cnt);
     char* out = desc->cols[c].base[P.dst];
     with_width(cw, [&](auto W_) {
 #pragma unroll
       for (int i = 0; i < IT; i++) {
         const int j = i * NT + (int)threadIdx.x;
         if (j < cnt)
-          #ifdef SRS_DIAG_SEQW
-          stw<decltype(W_)::value>(out + ((int64_t)j + ti.base) * (int64_t)cst, L.sval[j]);
-#elif defined(SRS_DIAG_WIN)
-          stw<decltype(W_)::value>(out + diag_win(j, dout[i]) * (int64_t)cst, L.sval[j]);
-#else
           stw<decltype(W_)::value>(out + ((int64_t)j + L.gdst[dout[i]]) * (int64_t)cst,
                                    L.sval[j]);
-#endif
       }
     });
   };
@@ -1732,13 +1591,11 @@ __device__ __forceinline__ void scatter_process_tile(
   } else {
     for (int c = 1; c < ncols; c++) move_col(c, v1);
   }
-  STAMP();  // 5: all stores issued (and, in stamp builds, drained)
-  STAMP_FLUSH(0);
 }
 
 // One tile per workgroup (XCD-aware order).
 template <typename KT, typename U, int LUT, bool CZ, bool PRE3>
-__global__ __launch_bounds__(kScatterThreads, SRS_SCATTER_WAVES_PER_EU) void scatter_kernel(
+__global__ __launch_bounds__(kScatterThreads, kScatterWavesPerEU) void scatter_kernel(
     const SortDesc* __restrict__ desc, const SegPlan* __restrict__ plan,
     const int32_t* __restrict__ tile_seg, const uint64_t* __restrict__ offs,
     const uint32_t* __restrict__ offs32, const GTile* __restrict__ gt) {
@@ -1753,8 +1610,7 @@ __global__ __launch_bounds__(kScatterThreads, SRS_SCATTER_WAVES_PER_EU) void sca
   if (ti.cnt == 0) return;
   // (the table is published by the barrier at the top of the tile)
   const DigitLut lut = stage_lut<LUT, kScatterThreads>(desc, slut);
-  scatter_process_tile<KT, U, LUT, CZ, PRE3>(desc, plan, L, ti, ncols, v0, v1, v2, my_off, lut,
-                                             offs, offs32);
+  scatter_process_tile<KT, U, LUT, CZ, PRE3>(desc, plan, L, ti, ncols, v0, v1, v2, my_off, lut);
 }
 
 // ---------------------------------------------------------------------------
@@ -2053,10 +1909,7 @@ __global__ __launch_bounds__(kPairThreads, 4) void scatter_pair_kernel(
 //   4. every column is staged in LDS in input order and written in output
 //      order: coalesced both ways, and safe in place.
 constexpr int kLocalBits = 9;      // digit of the LSD fallback passes
-#ifndef SRS_LOCAL_TOP_BITS
-#define SRS_LOCAL_TOP_BITS 11
-#endif
-constexpr int kLocalTopBits = SRS_LOCAL_TOP_BITS;  // bucket digit of the fast local kernel
+constexpr int kLocalTopBits = 11;                  // bucket digit of the fast local kernel
 constexpr int kLocalStableTopBits = 10;            // bucket digit of the stable fallback
 constexpr int kRankSortMax = 64;   // largest bucket the rank step takes
 
@@ -2174,8 +2027,6 @@ __device__ __forceinline__ bool local_fast_body(const SortDesc* __restrict__ des
   const int ncols = desc->ncols;
   const int kbytes = desc->key_bits >> 3;
   const uint64_t kmask = kbytes == 8 ? ~0ull : ((1ull << (8 * kbytes)) - 1);
-  STAMP_DECL
-  STAMP();
 
   if (threadIdx.x == 0) maxlen = 0;  // (first used after several barriers)
   for (uint32_t i = threadIdx.x; i < (uint32_t)(NB / 2); i += NT) hist2[i] = 0;
@@ -2203,13 +2054,9 @@ __device__ __forceinline__ bool local_fast_body(const SortDesc* __restrict__ des
 #pragma unroll
   for (int k = 0; k < IT; k++)
     if (valid(k)) vor |= ukey(k) ^ uref;
-  STAMP();  // 1: keys loaded
   wave_or_add(Ls.wor, wave, lane, (unsigned long long)vor);
-  STAMP();  // (diag) or reduced
   lds_barrier();
-  STAMP();  // (diag) barrier passed
   const unsigned long long var = wave_or_read(Ls.wor);
-  STAMP();  // (diag) var
 
   if (var != 0) {
     const int lo = __ffsll((long long)var) - 1;
@@ -2285,9 +2132,6 @@ __device__ __forceinline__ bool local_fast_body(const SortDesc* __restrict__ des
         }
       }
       lds_barrier();
-      STAMP();  // 2: stable bucket pass
-      STAMP();
-      STAMP();
     } else {
     // DIRECT: column 0 is exactly the key and the sort word holds every key
     // bit that varies, so the sorted keys are rebuilt from the words (no
@@ -2305,7 +2149,6 @@ __device__ __forceinline__ bool local_fast_body(const SortDesc* __restrict__ des
                         desc->cols[0].stride[BUF_IN] == (uint32_t)kbytes;
     auto bucket_rank = [&](auto DIRECT_) -> bool {
     constexpr bool DIRECT = decltype(DIRECT_)::value;
-    STAMP();  // (diag) direct decided
     // ---- 2. bucket pass on the top varying bits (LDS atomics on 16-bit
     // counters packed in pairs: 2^11 buckets in the LDS of 2^10 u32 ones) ----
 #pragma unroll
@@ -2315,9 +2158,7 @@ __device__ __forceinline__ bool local_fast_body(const SortDesc* __restrict__ des
         atomicAdd(&hist2[d >> 1], 1u << ((d & 1) << 4));
       }
     }
-    STAMP();  // (diag) atomics issued
     lds_barrier();
-    STAMP();  // (diag) barrier
     {
       uint32_t tb[BPT], tsum = 0;
 #pragma unroll
@@ -2329,7 +2170,6 @@ __device__ __forceinline__ bool local_fast_body(const SortDesc* __restrict__ des
       }
       uint32_t tot;
       uint32_t ex = block_excl_scan_1b<NT>(tsum, scan_sh, &tot);
-      STAMP();  // (diag) scanned
       int mymax = 0;
 #pragma unroll
       for (int q = 0; q < BPT; q += 2) {
@@ -2345,7 +2185,6 @@ __device__ __forceinline__ bool local_fast_body(const SortDesc* __restrict__ des
       block_max_into(&maxlen, mymax);
     }
     lds_barrier();
-    STAMP();  // 2: bucket histogram
     // CmpSorterNoSort: when every bucket (a node of the reference's bit
     // recursion, all keys sharing the bits above sh) holds <= leaf_skip keys,
     // the buckets are the leaves and stay in bucket-pass order
@@ -2369,7 +2208,6 @@ __device__ __forceinline__ bool local_fast_body(const SortDesc* __restrict__ des
     }
     if (threadIdx.x < (uint32_t)kRankSortMax) sbuf[cnt + threadIdx.x] = ~0ull;  // sentinels
     lds_barrier();
-    STAMP();  // 3: bucket scatter
     if (skip_rank) {  // the leaves unsorted: output slot p takes word p
       for (int p = (int)threadIdx.x; p < cnt; p += NT)
         perm[p] = DIRECT ? (uint16_t)p : (uint16_t)(sbuf[p] & ((1u << IDXB) - 1));
@@ -2380,7 +2218,7 @@ __device__ __forceinline__ bool local_fast_body(const SortDesc* __restrict__ des
     // The word orders by (key, original index), so the result is stable.
     // Slots in two halves bound register use; a wave-uniform trip count
     // keeps several LDS reads in flight.
-    constexpr int NH = SRS_LOCAL_RANK_SPLIT;
+    constexpr int NH = kLocalRankSplit;
     constexpr int H = IT / NH;
     if (DIRECT || !wide) {
 #pragma unroll
@@ -2468,7 +2306,6 @@ __device__ __forceinline__ bool local_fast_body(const SortDesc* __restrict__ des
       }
     }
     lds_barrier();
-    STAMP();  // 4: ranked
     return false;
     };  // bucket_rank
     if (direct) {
@@ -2501,7 +2338,6 @@ __device__ __forceinline__ bool local_fast_body(const SortDesc* __restrict__ des
                                 id[k] = (uint32_t)(w & imask);
                                 return (uint64_t)xf.inv((U)(top | (w >> IDXB)));
                               });
-        STAMP();  // 5: column 0 moved
         if constexpr (FW != 0) {  // exactly one payload column (or word pair)
           lds_barrier();  // every read of the words is done
 #pragma unroll
@@ -2538,8 +2374,6 @@ __device__ __forceinline__ bool local_fast_body(const SortDesc* __restrict__ des
       else if (desc->pair && (g.buf == BUF_TMP || g.buf == BUF_TMP2))
         direct_out(std::integral_constant<int, -1>{});
       else direct_out(std::integral_constant<int, 0>{});
-      STAMP();  // 6
-      STAMP_FLUSH(1);
       return false;
     }
     if (bucket_rank(std::false_type{})) return true;
@@ -2589,9 +2423,6 @@ __device__ __forceinline__ bool local_fast_body(const SortDesc* __restrict__ des
       x[3] = (uint32_t)(pv >> 32);
       __builtin_amdgcn_raw_buffer_store_b128(x, r, (uint32_t)(ebase + k * 64) * 16u, 0, 0);
     }
-    STAMP();
-    STAMP();
-    STAMP_FLUSH(1);
     return false;
   }
 
@@ -2621,7 +2452,6 @@ __device__ __forceinline__ bool local_fast_body(const SortDesc* __restrict__ des
   store_strip<IT>(desc->cols[0].base[BUF_OUT], desc->cols[0].width,
                   desc->cols[0].stride[BUF_OUT], base, ebase, cnt,
                   [&](int k) { return sbuf[id[k]]; });
-  STAMP();  // 5: column 0 moved
   if (pw) {
     lds_barrier();
 #pragma unroll
@@ -2644,8 +2474,6 @@ __device__ __forceinline__ bool local_fast_body(const SortDesc* __restrict__ des
                     desc->cols[c].stride[BUF_OUT], base, ebase, cnt,
                     [&](int k) { return sbuf[id[k]]; });
   }
-  STAMP();  // 6: columns moved
-  STAMP_FLUSH(1);
   return false;
 }
 
@@ -2756,8 +2584,7 @@ __global__ __launch_bounds__(NT, WPE) void local_direct_kernel(
 
   // ---- 1. keys ---------------------------------------------------------------
   uint64_t v0[IT];
-  load_strip<IT, true, KB, SRS_LOCAL_LOAD_AUX>(v0, desc->cols[0].base[g.buf], KB, KB, base, ebase,
-                                               cnt);
+  load_strip<IT, true, KB>(v0, desc->cols[0].base[g.buf], KB, KB, base, ebase, cnt);
   const U uref = xf((U)ldw<KB>(desc->cols[0].base[g.buf] + base * KB));
   auto ukey = [&](int k) -> U { return xf((U)v0[k]); };
   auto valid = [&](int k) -> bool { return ebase + k * 64 < cnt; };
@@ -2777,23 +2604,6 @@ __global__ __launch_bounds__(NT, WPE) void local_direct_kernel(
   const int lo = var ? __ffsll((long long)var) - 1 : 0;
   const int hi = var ? 63 - __clzll((long long)var) : 0;
   const int vbits = hi - lo + 1;
-#if SRS_DIRECT_WORD_DIGIT
-  // The bucket digit is the top kLocalTopBits bits of the sort word (key bits
-  // lo..hi above the 12-bit element index). With more varying key bits than
-  // that, these are the top varying key bits; with fewer (an "exact"
-  // segment: few distinct values, many copies each) the digit takes the top
-  // index bits too, which spreads each value's copies over buckets by input
-  // position, so buckets stay small and the rank by word (key, index) is the
-  // stable order: no separate exact pass.
-  constexpr bool EX = false;
-  if (var == 0 || vbits + IDXB > 64) {
-    hand_over(redo, redo_count);
-    return;
-  }
-  const bool exact = false;
-  const int nbits = kLocalTopBits;
-  const int dsh = vbits + IDXB - kLocalTopBits;  // the digit's position in a word
-#else
   // (EX: the exact pass is compiled in; it costs the other modes their
   // spill-free 128 VGPRs, and only the pair mode (C2's float keys with ~60
   // copies of each value) meets exact segments in bulk)
@@ -2805,7 +2615,6 @@ __global__ __launch_bounds__(NT, WPE) void local_direct_kernel(
   const bool exact = vbits <= kLocalTopBits;
   const int nbits = exact ? vbits : kLocalTopBits;
   const int dsh = hi - nbits + 1 - lo + IDXB;  // the digit's position in a word
-#endif
   const uint32_t mask = (1u << nbits) - 1;
   const uint64_t vmask = vbits == 64 ? ~0ull : ((1ull << vbits) - 1);
   // sort word: the varying key bits lo..hi above the element index (the bits
@@ -2922,7 +2731,7 @@ __global__ __launch_bounds__(NT, WPE) void local_direct_kernel(
     // ---- 4. rank inside each bucket, then every word to its sorted slot ------
     place = !skip_rank;
     if (!skip_rank) {
-      constexpr int NH = SRS_DIRECT_RANK_SPLIT;
+      constexpr int NH = kDirectRankSplit;
       constexpr int H = IT / NH;
 #pragma unroll
       for (int half = 0; half < NH; half++) {
@@ -2973,8 +2782,7 @@ __global__ __launch_bounds__(NT, WPE) void local_direct_kernel(
   }
   // the payloads (dense 8-byte words in every mode)
   uint64_t vn[IT];
-  load_strip<IT, true, 8, SRS_LOCAL_LOAD_AUX>(vn, desc->cols[1].base[g.buf], 8, 8, base, ebase,
-                                              cnt);
+  load_strip<IT, true, 8>(vn, desc->cols[1].base[g.buf], 8, 8, base, ebase, cnt);
   lds_barrier();
 
   // ---- 5. keys rebuilt from the sorted words, payloads staged ----------------
@@ -3511,12 +3319,6 @@ __global__ __launch_bounds__(NT) void small_sort_kernel(const SortDesc d, const 
     taken[0] = path >= 1;
     taken[1] = path >= 2;
   }
-#ifdef SRS_DIAG_TWICE
-  // diagnostic (timing only): the sort again over its own output, so that a
-  // kernel trace shows what a second, warm pass through the same code costs
-  __syncthreads();
-  small_bodies<KT, U, CZ, NT>(desc, Seg{g.start, g.len, g.rbits, BUF_OUT}, Ls);
-#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -3839,7 +3641,6 @@ __global__ __launch_bounds__(kLocalThreads) void mid_sort_kernel(
       ti.base = tbase;
       ti.cnt = cnt;
       ti.s = 0;
-      ti.t = w;
       const int64_t my_off = b < nb ? (int64_t)bs + pre : 0;
       scatter_process_tile<KT, U, 0, CZ, false>(desc, &Ls.level.plan, Ls.level.sc, ti, ncols, v0,
                                                  v1, v2, my_off, DigitLut{});
@@ -4161,7 +3962,6 @@ __global__ __launch_bounds__(kScatterThreads) void mid_level_kernel(
     ti.base = tbase;
     ti.cnt = cnt;
     ti.s = 0;
-    ti.t = t;
     scatter_process_tile<KT, U, 0, CZ, false>(desc, &L.plan, L.sc, ti, ncols, v0, v1, v2, my_off,
                                                DigitLut{});
   }
@@ -4390,7 +4190,7 @@ void launch_count(int key_size, const SortDesc* d, const SegPlan* plan,
                   const int32_t* tile_seg, int64_t ntiles, uint16_t* hist,
                   unsigned long long* var_or, unsigned long long* var_and, int lut,
                   hipStream_t st, const GTile* gt, const int32_t* torder) {
-  const unsigned grid = (unsigned)((ntiles + kCountTiles - 1) / kCountTiles);
+  const unsigned grid = (unsigned)ntiles;  // one tile per workgroup
 #define CALL(KT, U, CZ)                                                                 \
   if (lut == 2)                                                                         \
     count_kernel<KT, U, 2, CZ><<<grid, kCountThreads, 0, st>>>(                          \
