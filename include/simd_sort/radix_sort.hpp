@@ -365,6 +365,32 @@ void sort_ragged(void* stream, const SortIndex num, const SortIndex num_segments
                   payloads...);
 }
 
+// top_k_ragged: the first min(k, len) records of every segment [offsets[i],
+// offsets[i + 1]) of dense arrays of num records in one call
+// (srs_topk_ragged_soa_device). offsets is sort_ragged's; result j of
+// segment i lands at [i * k + j] of keys_out, of every payload_out and of
+// indices_out (positions inside the segment; may be null), slots from
+// min(k, len) on are not written; counts_out (device, num_segments entries;
+// may be null) receives min(k, len) per segment.
+template <bool Up = true, typename K, typename... Ps>
+void top_k_ragged(void* stream, const SortIndex k, const SortIndex num,
+                  const SortIndex num_segments, const int64_t* const offsets,
+                  const K* const keys, K* const keys_out, int64_t* const indices_out,
+                  int64_t* const counts_out, std::pair<const Ps*, Ps*>... payloads) {
+  static_assert(detail::key_kind<K>() >= 0, "unsupported key type");
+  static_assert((detail::valid_payload<Ps> && ...), "payload sizes must be 1, 2, 4 or 8");
+  static_assert(sizeof...(Ps) <= SRS_MAX_PAYLOADS, "too many payload arrays");
+  const void* pays[sizeof...(Ps) + 1] = {(const void*)payloads.first..., nullptr};
+  void* pays_out[sizeof...(Ps) + 1] = {(void*)payloads.second..., nullptr};
+  uint32_t sizes[sizeof...(Ps) + 1] = {(uint32_t)sizeof(Ps)..., 0};
+  detail::check(srs_topk_ragged_soa_device((int64_t)num, (int64_t)num_segments, offsets,
+                                           (int64_t)k, detail::key_kind<K>(), Up ? 1 : 0,
+                                           (const void*)keys, (int32_t)sizeof...(Ps), pays, sizes,
+                                           (void*)keys_out, pays_out, indices_out, counts_out,
+                                           stream),
+                "device::top_k_ragged");
+}
+
 }  // namespace device
 }  // namespace radix_sort
 }  // namespace simd_sort

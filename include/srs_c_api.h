@@ -295,6 +295,45 @@ int srs_sort_ragged_soa_device(int64_t num, int64_t num_segments, const int64_t*
                                void* keys_out, void* const* payloads_out,
                                int64_t* indices_out, void* stream);
 
+/* Ragged top-k: the first k records of every segment of a DEVICE array of
+ * offsets, in one call. The inputs are srs_sort_ragged_soa_device's: dense
+ * columns of num records, offsets holding num_segments + 1 int64 values in
+ * device memory; the inputs and the offsets are never written. The outputs
+ * hold num_segments * k records each, a fixed stride of k slots per segment:
+ * with c_i = min(k, len_i), result j < c_i of segment i is at i * k + j of
+ * every *_out column and of indices_out (may be NULL; positions inside the
+ * segment); slots j >= c_i are NOT written. counts_out (device int64,
+ * num_segments entries, may be NULL) receives c_i for every valid segment, 0
+ * for an empty one. Each segment's result is the first c_i records of its
+ * stable sort by transformed key (equal keys keep their input order; floats
+ * in the total order at every length; NaN keys are outside the contract; up
+ * == 0 gives the largest, descending): unique, and bit-equal to the head of
+ * srs_sort_ragged_soa_device's segment and to srs_topk_rows_soa_device when
+ * the offsets are uniform.
+ * Checked before any device access: key_kind, payload sizes, NULL or
+ * misaligned pointers (offsets, indices_out and counts_out: 8-byte aligned),
+ * num_segments + 1, num_segments * k and that product times a column width
+ * overflowing int64, 64 payload columns with indices (SRS_ERR_UNSUPPORTED),
+ * and any output (indices and counts included) over any input column or over
+ * the offsets array. num <= 0, num_segments <= 0 or k <= 0 is a no-op.
+ * Bad offsets behave as in srs_sort_ragged_soa_device: every kernel tests a
+ * segment's two offsets itself, a segment with a bad bound is skipped and
+ * counted, and when the count comes back non-zero the call returns
+ * SRS_ERR_INVALID_ARG (srs_last_error() names the count); the outputs are
+ * then unspecified. No column is accessed outside [0, num), no output
+ * outside its num_segments * k records.
+ * k <= 2048 (srs_topk_rows_max_k) with num < 2^31 takes three kernels, a wave
+ * per segment of up to 256 records and a workgroup per longer one, and ONE
+ * pinned read-back of the counters behind all of them. Other shapes run the
+ * ragged sort into workspace columns of num records (with its host waits)
+ * and copy the heads. */
+int srs_topk_ragged_soa_device(int64_t num, int64_t num_segments, const int64_t* offsets,
+                               int64_t k, int key_kind, int up, const void* keys,
+                               int32_t num_payloads, const void* const* payloads,
+                               const uint32_t* payload_sizes, void* keys_out,
+                               void* const* payloads_out, int64_t* indices_out,
+                               int64_t* counts_out, void* stream);
+
 /* ---- multi-GPU shard primitives (top-radix-bits partition) --
  * A node-wide sort of one array spread over N GPUs: every rank histograms
  * its keys' top bits (srs_key_histogram_device), the histograms are summed
@@ -601,6 +640,21 @@ int srs_debug_set_sort_ragged_short_max(int32_t len);
  * small-class / large-class / big list lengths as first read back, info[4] =
  * host read-backs during the call, info[5] = 1 if the prepare pass ran. */
 int srs_debug_last_sort_ragged(int64_t* info);
+
+/* Test hook, process-wide: the route srs_topk_ragged_soa_device takes. -1:
+ * the library's rule; 0: the kernels (k <= srs_topk_rows_max_k(), num <
+ * 2^31), 1: the ragged sort and the head copy. A call whose shape the forced
+ * route cannot take returns SRS_ERR_UNSUPPORTED; any other value of the hook
+ * returns SRS_ERR_INVALID_ARG. Needs no device. */
+int srs_debug_set_topk_ragged_route(int route);
+
+/* What the last ragged top-k on the current device did (synchronizes the
+ * device): info[0] = route, info[1] = segments of 1 .. 256 records (the wave
+ * kernel's), info[2] = longer segments (the list's), info[3] = the most
+ * select (histogram) passes any listed segment took (written by the kernel;
+ * 0 on the sort route), info[4] = host read-backs during the call, info[5] =
+ * kernel launches queued (-1 on the sort route: not counted). */
+int srs_debug_last_topk_ragged(int64_t* info);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 // srs_batch.hip — the batched calls on top of the sort driver (srs_driver.h):
-// top-k, row-wise top-k, row-wise sort and ragged sort, with their
-// out-of-place validation, C entry points and debug hooks.
+// top-k, row-wise top-k, row-wise sort, ragged sort and ragged top-k, with
+// their out-of-place validation, C entry points and debug hooks.
 #include <string.h>
 
 #include <algorithm>
@@ -573,18 +573,14 @@ int64_t ragged_list_cap(int64_t num, int64_t nseg, int short_max) {
   return std::min(nseg, num / ((int64_t)short_max + 1));
 }
 
-// R: the dense columns (R.num = num records each).
-int sort_ragged_device(const Request& R, int64_t nseg, const int64_t* offsets, int64_t* idx_out,
+// R: the dense columns (R.num = num records each). Under the caller's
+// workspace lock and WsUse; `what` names the call in the bad-offsets error,
+// *seen (or null) receives the classify pass's counters.
+int sort_ragged_locked(Workspace* W, const Request& R, int64_t nseg, const int64_t* offsets,
+                       int64_t* idx_out, int short_max, const char* what, ListCounters* seen,
                        hipStream_t st) {
-  int short_max = g_sort_ragged_short_max.load();
-  if (short_max < 0) short_max = kRowsWaveMax;
   const int64_t num = R.num;
   const int64_t cap = ragged_list_cap(num, nseg, short_max);
-  if ((nseg + 255) / 256 > 0x7fffffff)
-    return fail(SRS_ERR_UNSUPPORTED, "sort ragged: more than 2^39 segments");
-  WsScope ws;
-  SRS_TRY(ws.begin(st));
-  Workspace* W = ws.W;
   W->last_small = false;
   int64_t* info = W->sort_ragged_info;
   for (int i = 0; i < 6; i++) info[i] = 0;
@@ -627,9 +623,10 @@ int sort_ragged_device(const Request& R, int64_t nseg, const int64_t* offsets, i
   info[2] = (int64_t)c.n_local2;
   info[3] = (int64_t)c.n_big;
   info[0] = nseg - (int64_t)c.n_listed - (int64_t)c.n_empty - (int64_t)c.n_bad;
+  if (seen) *seen = c;
   if (c.n_bad > 0)
     return fail(SRS_ERR_INVALID_ARG,
-                "sort ragged: " + std::to_string(c.n_bad) +
+                std::string(what) + ": " + std::to_string(c.n_bad) +
                     " segment(s) with offsets that decrease or leave [0, num] (skipped; the "
                     "outputs are unspecified)");
   if (c.n_listed == 0) return SRS_OK;
@@ -650,6 +647,137 @@ int sort_ragged_device(const Request& R, int64_t nseg, const int64_t* offsets, i
   const LevelState S = level_state(d, ks, false, (int64_t)c.n_big, (int64_t)c.n_local,
                                    (int64_t)c.n_local2, (int64_t)c.n_copy);
   return list_finish(W, Q, d, d_desc, S, 0, false, &info[4], st);
+}
+
+int sort_ragged_device(const Request& R, int64_t nseg, const int64_t* offsets, int64_t* idx_out,
+                       hipStream_t st) {
+  int short_max = g_sort_ragged_short_max.load();
+  if (short_max < 0) short_max = kRowsWaveMax;
+  if ((nseg + 255) / 256 > 0x7fffffff)
+    return fail(SRS_ERR_UNSUPPORTED, "sort ragged: more than 2^39 segments");
+  WsScope ws;
+  SRS_TRY(ws.begin(st));
+  return sort_ragged_locked(ws.W, R, nseg, offsets, idx_out, short_max, "sort ragged", nullptr, st);
+}
+
+// ---------------------------------------------------------------------------
+// ragged top-k: the first min(k, len) records of every
+// segment of device offsets, at a stride of k slots per segment. Route 0 is
+// three kernels with everything decided on the device (classify, a wave per
+// short segment, a workgroup per listed long one) and one read-back of the
+// counters behind all of them; route 1 sorts the segments into workspace
+// columns (sort_ragged_locked) and copies the heads.
+// ---------------------------------------------------------------------------
+enum { TOPK_RAGGED_KERNELS = 0, TOPK_RAGGED_SORT = 1 };
+std::atomic<int> g_topk_ragged_route{-1};  // srs_debug_set_topk_ragged_route
+
+std::string topk_ragged_bad(unsigned long long n_bad) {
+  return "top-k ragged: " + std::to_string(n_bad) +
+         " segment(s) with offsets that decrease or leave [0, num] (skipped; the outputs are "
+         "unspecified)";
+}
+
+// R: the dense input columns (R.num = num records each); R.out_cols the
+// caller's outputs of nseg * k records.
+int topk_ragged_device(const Request& R, int64_t nseg, const int64_t* offsets, int64_t k,
+                       int64_t* idx_out, int64_t* counts_out, hipStream_t st) {
+  const int64_t num = R.num;
+  const bool can_kernels = k <= kTopkRowsMaxK && num < (int64_t(1) << 31);
+  int route = g_topk_ragged_route.load();
+  if (route < 0) route = can_kernels ? TOPK_RAGGED_KERNELS : TOPK_RAGGED_SORT;
+  else if (route == TOPK_RAGGED_KERNELS && !can_kernels)
+    return fail(SRS_ERR_UNSUPPORTED,
+                "top-k ragged: the kernel route takes k <= kTopkRowsMaxK and num < 2^31");
+  if ((nseg + 255) / 256 > 0x7fffffff)
+    return fail(SRS_ERR_UNSUPPORTED, "top-k ragged: more than 2^39 segments");
+  WsScope ws;
+  SRS_TRY(ws.begin(st));
+  Workspace* W = ws.W;
+  int64_t* info = W->topk_ragged_info;
+  for (int i = 0; i < 6; i++) info[i] = 0;
+  info[0] = route;
+  const int ks = key_size_of(R.kind);
+  const SortDesc kd = init_desc(R.kind, R.up);
+
+  TopkRaggedArgs a;
+  init_rows_args(a, R, idx_out);
+  a.num = num;
+  a.nseg = nseg;
+  a.k = k;
+  a.offsets = offsets;
+  a.key_bits = kd.key_bits;
+  a.mpos = kd.mpos;
+  a.mneg = kd.mneg;
+  a.counts_out = counts_out;
+  SRS_TRY(ensure(W->tkrctr, sizeof(TopkRaggedCounters)));
+  a.ctr = (TopkRaggedCounters*)W->tkrctr.p;
+  HIP_TRY(hipMemsetAsync(a.ctr, 0, sizeof(TopkRaggedCounters), st));
+
+  if (route == TOPK_RAGGED_SORT) {
+    // ---- the ragged sort into workspace columns, then the heads ---------------
+    info[5] = -1;
+    {
+      TimedScope ts("topk_ragged_classify", (double)nseg, st);
+      HIP_TRY(launch_topk_ragged_classify(a, st));  // (counts_out only: nothing is listed)
+    }
+    const int nsc = R.ncols + (idx_out ? 1 : 0);
+    size_t off[SRS_MAX_COLS + 1], bytes = 0;
+    for (int c = 0; c < nsc; c++) {
+      off[c] = bytes;
+      bytes += align_up((size_t)num * (c < R.ncols ? R.widths[c] : 8), 256);
+    }
+    SRS_TRY(ensure(W->tkrcols, bytes, ws_alloc_mode()));
+    char* cols = (char*)W->tkrcols.p;
+    Request Q = R;
+    Q.thresh = 0;
+    for (int c = 0; c < R.ncols; c++) Q.out_cols[c] = cols + off[c];
+    int64_t* idx_ws = idx_out ? (int64_t*)(cols + off[R.ncols]) : nullptr;
+    ListCounters seen{};
+    const int rc = sort_ragged_locked(W, Q, nseg, offsets, idx_ws, kRowsWaveMax, "top-k ragged",
+                                      &seen, st);
+    info[1] = W->sort_ragged_info[0];
+    info[2] = (int64_t)std::min<unsigned long long>(seen.n_listed, (unsigned long long)nseg);
+    info[4] = W->sort_ragged_info[4];
+    SRS_TRY(rc);
+    for (int c = 0; c < R.ncols; c++) a.col[c].in = cols + off[c];
+    a.idx_in = idx_ws;
+    TimedScope ts("topk_ragged_heads", (double)num, st);
+    HIP_TRY(launch_topk_ragged_heads(a, st));
+    return SRS_OK;
+  }
+
+  // ---- classify, the wave kernel, the list's workgroups, one read-back -------
+  const int64_t list_cap = ragged_list_cap(num, nseg, kRowsWaveMax);
+  SRS_TRY(ensure(W->tkrlist, (size_t)std::max<int64_t>(list_cap, 1) * sizeof(int64_t)));
+  a.list = (int64_t*)W->tkrlist.p;
+  a.list_cap = (unsigned long long)list_cap;
+  if (!W->h_tkr)
+    HIP_TRY(hipHostMalloc((void**)&W->h_tkr, sizeof(TopkRaggedCounters), hipHostMallocDefault));
+  if (!W->ev_ragged) HIP_TRY(hipEventCreateWithFlags(&W->ev_ragged, hipEventDisableTiming));
+  {
+    TimedScope ts("topk_ragged_classify", (double)nseg, st);
+    HIP_TRY(launch_topk_ragged_classify(a, st));
+  }
+  {
+    TimedScope ts("topk_ragged_short", (double)num, st);
+    HIP_TRY(launch_topk_ragged_short(ks, a, st));
+  }
+  info[5] = 2;
+  if (list_cap > 0) {
+    TimedScope ts("topk_ragged_long", (double)num, st);
+    HIP_TRY(launch_topk_ragged_long(ks, a, st));
+    info[5] = 3;
+  }
+  HIP_TRY(hipMemcpyAsync(W->h_tkr, a.ctr, sizeof(TopkRaggedCounters), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipEventRecord(W->ev_ragged, st));
+  SRS_TRY(event_poll(W->ev_ragged));
+  const TopkRaggedCounters c = *W->h_tkr;
+  info[1] = (int64_t)c.n_short;
+  info[2] = (int64_t)c.n_long;
+  info[3] = (int64_t)c.max_passes;
+  info[4] = 1;
+  if (c.n_bad > 0) return fail(SRS_ERR_INVALID_ARG, topk_ragged_bad(c.n_bad));
+  return SRS_OK;
 }
 
 }  // namespace
@@ -725,6 +853,67 @@ int srs_sort_ragged_soa_device(int64_t num, int64_t num_segments, const int64_t*
   if (outputs_overlap(R, indices_out, num, offsets, ((size_t)num_segments + 1) * sizeof(int64_t)))
     return fail(SRS_ERR_INVALID_ARG, "sort ragged outputs must not overlap the offsets");
   return sort_ragged_device(R, num_segments, offsets, indices_out, (hipStream_t)stream);
+}
+
+int srs_topk_ragged_soa_device(int64_t num, int64_t num_segments, const int64_t* offsets,
+                               int64_t k, int key_kind, int up, const void* keys,
+                               int32_t num_payloads, const void* const* payloads,
+                               const uint32_t* payload_sizes, void* keys_out,
+                               void* const* payloads_out, int64_t* indices_out,
+                               int64_t* counts_out, void* stream) {
+  Request R;
+  SRS_TRY(build_soa(R, num, key_kind, up, 0, (void*)keys, num_payloads, (void* const*)payloads,
+                    payload_sizes, keys_out, payloads_out));
+  const bool work = num > 0 && num_segments > 0 && k > 0;
+  int64_t slots = 0;
+  const char* shape = !work ? nullptr
+                      : num_segments > (INT64_MAX >> 4) ? "num_segments + 1 overflows"
+                      : __builtin_mul_overflow(num_segments, k, &slots) || slots > (INT64_MAX >> 4)
+                          ? "num_segments * k overflows"
+                          : nullptr;
+  SRS_TRY(validate_outputs(R, {"top-k ragged", keys_out, indices_out, work ? num : 0,
+                               work ? (shape ? 1 : slots) : 0, true, shape}));
+  if (!work) return SRS_OK;
+  if (!offsets) return fail(SRS_ERR_INVALID_ARG, "offsets is NULL");
+  if ((uintptr_t)offsets % 8 != 0) return fail(SRS_ERR_INVALID_ARG, "offsets must be 8-byte aligned");
+  if ((uintptr_t)counts_out % 8 != 0)
+    return fail(SRS_ERR_INVALID_ARG, "counts_out must be 8-byte aligned");
+  const size_t offs_bytes = ((size_t)num_segments + 1) * sizeof(int64_t);
+  if (outputs_overlap(R, indices_out, slots, offsets, offs_bytes))
+    return fail(SRS_ERR_INVALID_ARG, "top-k ragged outputs must not overlap the offsets");
+  if (counts_out) {
+    // counts_out: one more output of num_segments int64 (outputs_overlap's test)
+    const uintptr_t x = (uintptr_t)counts_out;
+    const size_t xn = (size_t)num_segments * sizeof(int64_t);
+    auto over = [&](const void* p, size_t bytes) {
+      const uintptr_t y = (uintptr_t)p;
+      return bytes && x < y + bytes && y < x + xn;
+    };
+    for (int c = 0; c < R.ncols; c++)
+      if (over(R.in_cols[c], (size_t)num * R.widths[c]))
+        return fail(SRS_ERR_INVALID_ARG, "top-k ragged counts_out must not overlap the inputs");
+    if (over(offsets, offs_bytes))
+      return fail(SRS_ERR_INVALID_ARG, "top-k ragged counts_out must not overlap the offsets");
+  }
+  return topk_ragged_device(R, num_segments, offsets, k, indices_out, counts_out,
+                            (hipStream_t)stream);
+}
+
+int srs_debug_set_topk_ragged_route(int route) {
+  if (route < -1 || route > TOPK_RAGGED_SORT)
+    return fail(SRS_ERR_INVALID_ARG, "route must be -1, 0 or 1");
+  g_topk_ragged_route.store(route);
+  return SRS_OK;
+}
+
+int srs_debug_last_topk_ragged(int64_t* info) {
+  if (!info) return fail(SRS_ERR_INVALID_ARG, "info is NULL");
+  Workspace* W = nullptr;
+  WsLock lk;
+  SRS_TRY(acquire_ws(&W, &lk));
+  HIP_TRY(hipDeviceSynchronize());
+  for (int i = 0; i < 6; i++) info[i] = W->topk_ragged_info[i];
+  return SRS_OK;
 }
 
 int srs_debug_set_topk_candidates(int64_t max_candidates) {

@@ -94,6 +94,11 @@ struct Workspace {
   // ragged sort: what the last call did; the event behind its counter copy
   int64_t sort_ragged_info[6] = {0, 0, 0, 0, 0, 0};
   hipEvent_t ev_ragged = nullptr;
+  // ragged top-k: the device counters and their pinned copy, the list of long
+  // segments, the sort route's columns of num records; what the last call did
+  DevBuf tkrctr, tkrlist, tkrcols;
+  TopkRaggedCounters* h_tkr = nullptr;
+  int64_t topk_ragged_info[6] = {0, 0, 0, 0, 0, 0};
   hipStream_t side = nullptr;  // medium sorts: the large local class's stream
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   ListCounters* h_ctr = nullptr;

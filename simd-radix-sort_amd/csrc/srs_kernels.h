@@ -260,4 +260,52 @@ hipError_t launch_ragged_segs(const int64_t* offsets, int64_t nseg, int64_t num,
 // written.
 hipError_t launch_ragged_prepare(const RaggedArgs& a, hipStream_t st);
 
+// ---- ragged top-k --------------------------------------------
+// The first min(k, len) records of every segment of §14's offsets: result j of
+// segment i is at i * k + j of col[].out (and of idx_out), a fixed stride of k
+// slots per segment; slots from min(k, len) on are never written. Validity
+// is §14's: every kernel tests a segment's two offsets itself.
+struct TopkRaggedCounters {
+  unsigned long long n_bad;      // segments with a bad bound, or past the list's capacity
+  unsigned long long n_empty;
+  unsigned long long n_short;    // valid, 1 .. kRowsWaveMax records: the wave kernel's
+  unsigned long long n_long;     // valid and longer: entries of the list
+  unsigned long long n_offer;    // long segments that asked for a list slot
+  unsigned long long max_passes; // the most select passes any listed segment took
+};
+struct TopkRaggedArgs {
+  int64_t num, nseg, k;
+  const int64_t* offsets;
+  int32_t ncols;
+  int32_t key_bits;
+  uint64_t mpos, mneg;  // SortDesc's key transform
+  int32_t cap;          // the long kernel's LDS slots (launch-wide, from k alone)
+  int64_t* idx_out;     // or null
+  int64_t* counts_out;  // or null: min(k, len) per valid segment, 0 for the others
+  // the indices of the segments longer than kRowsWaveMax, list_cap entries
+  // (null: nothing is listed, the sort route)
+  int64_t* list;
+  unsigned long long list_cap;
+  TopkRaggedCounters* ctr;  // zeroed by the caller
+  // the sort route's head copy: the sorted columns are col[].in, and the
+  // sorted in-segment positions idx_in (or null)
+  const int64_t* idx_in;
+  TopkRowsCol col[SRS_MAX_COLS];
+};
+// One thread per segment: counts_out, the counters, and the list of long
+// segments. At most list_cap segments are listed (valid offsets give no more
+// than num / (kRowsWaveMax + 1) long segments); any further one counts as bad.
+hipError_t launch_topk_ragged_classify(const TopkRaggedArgs& a, hipStream_t st);
+// One wave per segment: every valid segment of 1 .. kRowsWaveMax records
+// sorted whole in LDS, its first min(k, len) records written.
+hipError_t launch_topk_ragged_short(int key_size, const TopkRaggedArgs& a, hipStream_t st);
+// One workgroup per listed segment, grid-stride over the list, whose length
+// it reads from a.ctr->n_long: §12's streamed select with the segment's own
+// length. Fills a.cap from a.k (k <= kTopkRowsMaxK, num < 2^31).
+hipError_t launch_topk_ragged_long(int key_size, TopkRaggedArgs& a, hipStream_t st);
+// The sort route: record j < min(k, len) of every valid segment copied from
+// col[].in + (start + j) to col[].out + (i * k + j) (idx_in to idx_out
+// likewise), element-parallel over [0, num).
+hipError_t launch_topk_ragged_heads(const TopkRaggedArgs& a, hipStream_t st);
+
 }  // namespace srs

@@ -5711,4 +5711,438 @@ hipError_t launch_ragged_prepare(const RaggedArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// ragged top-k (srs_topk_ragged_soa_device): §12's select per
+// segment of §14's offsets. Three plain kernels in stream order (classify,
+// the wave kernel for segments of up to kRowsWaveMax records, the workgroup
+// kernel over the list of longer ones), and the sort route's head copy. Each
+// reads a segment's two offsets itself and skips the segment unless 0 <=
+// start <= end <= num; no workgroup reads what another wrote in the same
+// launch.
+// ---------------------------------------------------------------------------
+constexpr int kTopkRaggedThreads = 256;      // classify, the wave kernel, the head copy
+constexpr int kTopkRaggedItems = 4;          // the head copy's records per thread
+constexpr int kTopkRaggedLongThreads = 1024;
+
+// rows_write for the first c records of a segment of n at `at` of the input
+// columns, to slots out0 .. out0 + c of the outputs: result j is input
+// record si[j] of the segment.
+template <typename KT>
+__device__ __forceinline__ void topk_ragged_write(const TopkRaggedArgs& A, int64_t at,
+                                                  int64_t out0, uint32_t n, uint32_t c,
+                                                  const uint32_t* si, uint32_t t, uint32_t nt) {
+  constexpr int KS = (int)sizeof(KT);
+  for (uint32_t j = t; j < c; j += nt) {
+    const uint32_t e = si[j];
+    if (e >= n) continue;  // (a padding slot: never inside the first c)
+    stw<KS>(A.col[0].out + (out0 + j) * KS, (uint64_t)gld<KT>(A.col[0].in + (at + e) * KS));
+    if (A.idx_out) gst<int64_t>(A.idx_out + out0 + j, (int64_t)e);
+  }
+  for (int q = 1; q < A.ncols; q++) {
+    const TopkRowsCol& C = A.col[q];
+    with_width(C.width, [&](auto W_) {
+      constexpr int W = decltype(W_)::value;
+      for (uint32_t j = t; j < c; j += nt) {
+        const uint32_t e = si[j];
+        if (e < n) stw<W>(C.out + (out0 + j) * W, ldw<W>(C.in + (at + e) * W));
+      }
+    });
+  }
+}
+
+// One thread per segment: counts_out, the bad / empty / short / long counts
+// (one atomic per wave and counter), and the list of the long segments, whose
+// slots a wave takes with one atomic. A segment past the list's capacity can
+// only come from offsets that are not non-decreasing: it counts as bad.
+__global__ __launch_bounds__(kTopkRaggedThreads) void topk_ragged_classify_kernel(
+    const int64_t* __restrict__ offsets, int64_t nseg, int64_t num, int64_t k,
+    int64_t* __restrict__ counts_out, int64_t* __restrict__ list, unsigned long long list_cap,
+    TopkRaggedCounters* __restrict__ ctr) {
+  const int64_t s = (int64_t)blockIdx.x * kTopkRaggedThreads + threadIdx.x;
+  int64_t at = 0, len = 0;
+  bool bad = false, lng = false;
+  if (s < nseg) {
+    bad = !ragged_bounds(offsets, s, num, &at, &len);
+    if (bad) len = 0;
+    lng = len > kRowsWaveMax;
+  }
+  if (list) {
+    const uint64_t mo = __ballot(lng);
+    if (mo) {  // (uniform over the wave)
+      unsigned long long base = 0;
+      if (lane_id() == 0) base = atomicAdd(&ctr->n_offer, (unsigned long long)__popcll(mo));
+      base = __shfl(base, 0, 64);
+      if (lng) {
+        const unsigned long long slot = base + popc_below(mo);
+        if (slot < list_cap) {
+          list[slot] = s;
+        } else {
+          lng = false;
+          bad = true;
+          len = 0;
+        }
+      }
+    }
+  }
+  const bool empty = s < nseg && !bad && len == 0;
+  const bool shrt = len >= 1 && !lng;
+  const uint64_t mb = __ballot(bad), me = __ballot(empty), ms = __ballot(shrt), ml = __ballot(lng);
+  if (lane_id() == 0) {
+    if (mb) atomicAdd(&ctr->n_bad, (unsigned long long)__popcll(mb));
+    if (me) atomicAdd(&ctr->n_empty, (unsigned long long)__popcll(me));
+    if (ms) atomicAdd(&ctr->n_short, (unsigned long long)__popcll(ms));
+    if (ml) atomicAdd(&ctr->n_long, (unsigned long long)__popcll(ml));
+  }
+  if (s < nseg && counts_out) counts_out[s] = min(k, len);
+}
+
+// ragged_short_kernel writing a head: one WAVE per segment, four to a
+// workgroup, no workgroup barrier. The segment is sorted whole in the wave's
+// slab; only its first min(k, len) records are written, by sorted position,
+// straight from the caller's input.
+template <typename KT, typename U>
+__global__ __launch_bounds__(kTopkRaggedThreads) void topk_ragged_short_kernel(
+    const TopkRaggedArgs A) {
+  constexpr int KS = (int)sizeof(KT);
+  constexpr int WPB = kTopkRaggedThreads / 64;
+  __shared__ U tkr_sk[WPB * kRowsWaveMax];
+  __shared__ uint32_t tkr_si[WPB * kRowsWaveMax];
+  const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
+  const int64_t s = (int64_t)blockIdx.x * WPB + wave;
+  if (s >= A.nseg) return;  // (whole waves: nothing below waits for another wave)
+  int64_t at, len;
+  if (!ragged_bounds(A.offsets, s, A.num, &at, &len)) return;
+  if (len < 1 || len > kRowsWaveMax) return;
+  const uint32_t n = (uint32_t)len;
+  uint32_t p2 = 2;
+  while (p2 < n) p2 <<= 1;
+  U* const sk = tkr_sk + wave * kRowsWaveMax;
+  uint32_t* const si = tkr_si + wave * kRowsWaveMax;
+  SelectArgs a;
+  a.key_bits = A.key_bits;
+  a.mpos = A.mpos;
+  a.mneg = A.mneg;
+  const Xform<U> xf = select_xform<U>(a);
+  const char* keys = A.col[0].in + at * KS;
+  for (uint32_t e = lane; e < p2; e += 64) {
+    const bool ok = e < n;
+    sk[e] = ok ? xf((U)gld<KT>(keys + (int64_t)e * KS)) : (U)~(U)0;
+    si[e] = ok ? e : 0xffffffffu;
+  }
+  wave_lds_sync();
+  rows_bitonic(sk, si, p2, lane, 64u, [] { wave_lds_sync(); });
+  topk_ragged_write<KT>(A, at, s * A.k, n, (uint32_t)min((int64_t)n, A.k), si, lane, 64u);
+}
+
+// topk_rows_kernel's streamed form with the segment's own length and start:
+// one workgroup per listed segment, grid-stride over the list. The list's
+// length and the segment's bounds are read from memory no kernel of the call
+// writes after the classify pass, the same way in every thread, so the trip
+// counts and every condition around a barrier are uniform over the workgroup.
+// A.cap slots (>= 2 k): a segment of at most A.cap records is sorted whole,
+// with no histogram pass.
+template <typename KT, typename U, int NT>
+__global__ __launch_bounds__(NT) void topk_ragged_long_kernel(const TopkRaggedArgs A) {
+  constexpr int KS = (int)sizeof(KT);
+  constexpr int NW = NT / 64;
+  constexpr int TILE = NT * kRowItems;
+  constexpr int NB = 1 << kHistMaxBits;
+  constexpr int BPT = NB / NT > 0 ? NB / NT : 1;  // histogram bins a thread sums
+  constexpr uint32_t kSpare = (uint32_t)NB;
+  static_assert(NB % NT == 0, "the bin walk gives every thread whole bins");
+  static_assert(kRowItems * NW <= NT, "one thread per (slot, wave) count");
+  extern __shared__ __attribute__((aligned(16))) unsigned char topk_ragged_lds[];
+  __shared__ uint32_t scan_sh[NW + 1];
+  __shared__ uint32_t wcnt[kRowItems * NW];  // per (slot, wave): sure | candidates << 16
+  __shared__ unsigned long long bc[5];       // bucket, records below it, its size, OR, inverted AND
+  U* const sk = (U*)topk_ragged_lds;               // [cap] transformed keys of the selected records
+  uint32_t* const si = (uint32_t*)(sk + A.cap);    // [cap] their positions in the segment
+  uint32_t* const h = si + A.cap;                  // [NB]
+  const int t = (int)threadIdx.x, wave = t >> 6;
+  const int kb = A.key_bits;
+  const uint64_t kmask = kb == 64 ? ~0ull : ((1ull << kb) - 1);
+  const uint32_t cap = (uint32_t)A.cap;
+  const unsigned long long nlist = min(gld<unsigned long long>(&A.ctr->n_long), A.list_cap);
+
+  for (unsigned long long li = blockIdx.x; li < nlist; li += gridDim.x) {
+    const int64_t seg = A.list[li];
+    // (an entry of this call's classify pass: 0 <= seg < nseg, and a valid
+    // segment's len <= num < 2^31; uniform, every thread read the same words)
+    int64_t at, len;
+    if (!ragged_bounds(A.offsets, seg, A.num, &at, &len)) continue;
+    const uint32_t n = (uint32_t)len, kk = (uint32_t)min(len, A.k);
+    SelectArgs a;
+    a.keys = A.col[0].in + at * KS;
+    a.stride = (uint32_t)KS;
+    a.n = n;
+    a.key_bits = kb;
+    a.mpos = A.mpos;
+    a.mneg = A.mneg;
+    const Xform<U> xf = select_xform<U>(a);
+    U raw[kRowItems];
+
+    // ---- which records: the prefix of the boundary bucket --------------------
+    uint64_t prefix = 0;        // the fixed top bits, in place
+    int fixed = 0, top = kb;    // the next digit ends below bit `top`
+    uint32_t k_rem = kk, cand = n;  // the rank wanted inside the prefix's bucket; its size
+    bool resolved = false;      // the bucket's keys are all equal
+    uint32_t passes = 0;
+    while (!resolved && cand != k_rem && (kk - k_rem) + cand > cap) {
+      const int bits = min(kHistMaxBits, top), shift = top - bits;
+      const bool all = fixed == 0;
+      const int psh = all ? 0 : kb - fixed;
+      const U pv = all ? (U)0 : (U)(prefix >> psh);
+      const uint32_t nb = 1u << bits, mask = nb - 1;
+      for (uint32_t i = t; i < nb; i += NT) h[i] = 0;
+      if (t < 5) bc[t] = 0;
+      __syncthreads();
+      U vor = 0, vnand = 0;
+      for (uint32_t base = 0; base < n; base += TILE) {
+        const int cnt = (int)min((uint32_t)TILE, n - base);
+        select_load<KT, U, true, NT, kRowItems>(a, base, cnt, raw);
+        const bool full = cnt == TILE;  // (a partial tile is always read in element order)
+#pragma unroll
+        for (int q = 0; q < kRowItems; q++) {
+          const U u = xf(raw[q]);
+          const bool ok = (full || q * NT + t < cnt) && (all || (U)(u >> psh) == pv);
+          vor |= ok ? u : (U)0;
+          vnand |= ok ? (U)~u : (U)0;
+          select_hist_add(h, ok ? ((uint32_t)(u >> shift) & mask) : kSpare, kSpare);
+        }
+      }
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) {
+        vor |= __shfl_xor(vor, o, 64);
+        vnand |= __shfl_xor(vnand, o, 64);
+      }
+      if (lane_id() == 0) {
+        atomicOr(&bc[3], (unsigned long long)vor);
+        atomicOr(&bc[4], (unsigned long long)vnand);
+      }
+      __syncthreads();
+      {  // the bucket that holds rank k_rem: a block scan over the threads' bin sums
+        uint32_t c[BPT], s = 0;
+#pragma unroll
+        for (int i = 0; i < BPT; i++) {
+          const uint32_t bin = (uint32_t)(t * BPT + i);
+          c[i] = bin < nb ? h[bin] : 0u;
+          s += c[i];
+        }
+        uint32_t tot;
+        uint32_t below = block_excl_scan<NT>(s, scan_sh, &tot);
+        if (below < k_rem && k_rem <= below + s) {
+#pragma unroll
+          for (int i = 0; i < BPT; i++) {
+            if (below + c[i] >= k_rem) {
+              bc[0] = (unsigned long long)(t * BPT + i);
+              bc[1] = below;
+              bc[2] = c[i];
+              break;
+            }
+            below += c[i];
+          }
+        }
+      }
+      __syncthreads();
+      const uint64_t b = bc[0], hor = bc[3], hnand = bc[4];
+      k_rem -= (uint32_t)bc[1];
+      cand = (uint32_t)bc[2];
+      __syncthreads();  // (bc and h are written again by the next pass)
+      passes++;
+      prefix |= b << shift;
+      fixed = kb - shift;
+      // where the bucket's parent still varies below this digit: the next
+      // digit starts at its highest varying bit, the bits between are shared
+      const uint64_t low = (1ull << shift) - 1;  // (shift <= 52)
+      const uint64_t vand = ~hnand & kmask;
+      const uint64_t var = (hor ^ vand) & low;
+      if (var == 0) {
+        resolved = true;
+        prefix |= vand & low;
+        fixed = kb;
+      } else {
+        const int hb = 63 - __builtin_clzll(var);
+        if (cand != k_rem && (kk - k_rem) + cand > cap) {
+          prefix |= vand & low & ~((2ull << hb) - 1);
+          fixed = kb - (hb + 1);
+          top = hb + 1;
+        }
+      }
+    }
+
+    // ---- the selected records into LDS, in input order -----------------------
+    // everything below the prefix, and the bucket itself (a bucket of equal
+    // keys: only its first k_rem records)
+    const bool all = fixed == 0;
+    const int psh = all ? 0 : kb - fixed;
+    const U pv = all ? (U)0 : (U)(prefix >> psh);
+    const uint32_t nsure = kk - k_rem;
+    const uint32_t climit = resolved ? k_rem : cand;
+    const uint32_t m = min(nsure + climit, cap);  // (never above cap: the stop rule)
+    uint32_t rs = 0, rc = 0;  // sure records / candidates before this tile
+    for (uint32_t base = 0; base < n; base += TILE) {
+      const int cnt = (int)min((uint32_t)TILE, n - base);
+      select_load<KT, U, false, NT, kRowItems>(a, base, cnt, raw);
+#pragma unroll
+      for (int q = 0; q < kRowItems; q++) raw[q] = xf(raw[q]);
+      uint32_t cls = 0;  // 2 bits per slot: 1 sure, 2 candidate
+      uint32_t rk[kRowItems];
+#pragma unroll
+      for (int q = 0; q < kRowItems; q++) {
+        const bool ok = q * NT + t < cnt;
+        const U x = (U)(raw[q] >> psh);
+        const bool s = ok && !all && x < pv;
+        const bool c = ok && (all || x == pv);
+        const uint64_t bs = __ballot(s), bcand = __ballot(c);
+        rk[q] = popc_below(s ? bs : bcand);
+        cls |= (s ? 1u : c ? 2u : 0u) << (2 * q);
+        if (lane_id() == 0) wcnt[q * NW + wave] = (uint32_t)__popcll(bs) | ((uint32_t)__popcll(bcand) << 16);
+      }
+      __syncthreads();
+      uint32_t tot;
+      const uint32_t v = t < kRowItems * NW ? wcnt[t] : 0u;
+      const uint32_t pre = block_excl_scan<NT>(v, scan_sh, &tot);  // (a tile's counts stay below 2^16)
+      if (t < kRowItems * NW) wcnt[t] = pre;
+      __syncthreads();
+#pragma unroll
+      for (int q = 0; q < kRowItems; q++) {
+        const uint32_t c = (cls >> (2 * q)) & 3u;
+        const uint32_t p = wcnt[q * NW + wave];
+        const uint32_t rank_c = rc + (p >> 16) + rk[q];
+        const uint32_t slot = c == 1 ? rs + (p & 0xffffu) + rk[q] : nsure + rank_c;
+        if ((c == 1 || (c == 2 && rank_c < climit)) && slot < m) {
+          sk[slot] = raw[q];
+          si[slot] = base + (uint32_t)(q * NT + t);
+        }
+      }
+      rs += tot & 0xffffu;
+      rc += tot >> 16;
+      __syncthreads();  // (wcnt is written again by the next tile)
+      if (rs >= nsure && rc >= climit) break;
+    }
+
+    // ---- sort by (key, position), padded to a power of two ---------------------
+    uint32_t p2 = 1;
+    while (p2 < m) p2 <<= 1;
+    for (uint32_t i = m + t; i < p2; i += NT) {
+      sk[i] = (U)~(U)0;
+      si[i] = 0xffffffffu;
+    }
+    __syncthreads();
+    rows_bitonic(sk, si, p2, (uint32_t)t, (uint32_t)NT, [] { __syncthreads(); });
+
+    // ---- the first kk records, every column read by position -----------------
+    topk_ragged_write<KT>(A, at, seg * A.k, n, kk, si, (uint32_t)t, (uint32_t)NT);
+    if (t == 0 && passes > (uint32_t)gld<unsigned long long>(&A.ctr->max_passes))
+      atomicMax(&A.ctr->max_passes, (unsigned long long)passes);
+    __syncthreads();  // (the LDS slots are the next segment's)
+  }
+}
+
+// The sort route's head copy, element-parallel over [0, num) as
+// ragged_prepare_kernel is: a thread finds its record's segment by a search
+// of the offsets, tests the bounds found before anything is touched, and
+// copies the record when it lies among the first k of a valid segment.
+__global__ __launch_bounds__(kTopkRaggedThreads) void topk_ragged_heads_kernel(
+    const TopkRaggedArgs A) {
+  const int64_t e0 = (int64_t)blockIdx.x * (kTopkRaggedThreads * kTopkRaggedItems) + threadIdx.x;
+  int64_t dst[kTopkRaggedItems];  // the output slot, or -1: not copied
+  int64_t at = 0, len = -1, seg = 0;  // the segment of the previous record (len < 0: none)
+#pragma unroll
+  for (int q = 0; q < kTopkRaggedItems; q++) {
+    const int64_t e = e0 + q * kTopkRaggedThreads;
+    dst[q] = -1;
+    if (e >= A.num) continue;
+    if (len < 0 || e < at || e - at >= len) {
+      int64_t lo = 0, hi = A.nseg;
+      while (hi - lo > 1) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (A.offsets[mid] <= e) lo = mid;
+        else hi = mid;
+      }
+      seg = lo;
+      if (!ragged_bounds(A.offsets, lo, A.num, &at, &len)) len = -1;
+    }
+    if (len > 0 && e >= at && e - at < len && e - at < A.k) dst[q] = seg * A.k + (e - at);
+  }
+  for (int c = 0; c < A.ncols; c++) {
+    const TopkRowsCol C = A.col[c];
+    with_width(C.width, [&](auto W_) {
+      constexpr int W = decltype(W_)::value;
+      uint64_t v[kTopkRaggedItems] = {};
+#pragma unroll
+      for (int q = 0; q < kTopkRaggedItems; q++)
+        if (dst[q] >= 0) v[q] = ldw<W>(C.in + (e0 + q * kTopkRaggedThreads) * W);
+#pragma unroll
+      for (int q = 0; q < kTopkRaggedItems; q++)
+        if (dst[q] >= 0) stw<W>(C.out + dst[q] * W, v[q]);
+    });
+  }
+  if (A.idx_out && A.idx_in) {
+#pragma unroll
+    for (int q = 0; q < kTopkRaggedItems; q++)
+      if (dst[q] >= 0)
+        gst<int64_t>(A.idx_out + dst[q], gld<int64_t>(A.idx_in + e0 + q * kTopkRaggedThreads));
+  }
+}
+
+hipError_t launch_topk_ragged_classify(const TopkRaggedArgs& a, hipStream_t st) {
+  const int64_t grid = (a.nseg + kTopkRaggedThreads - 1) / kTopkRaggedThreads;
+  if (grid <= 0 || grid > 0x7fffffff || a.k < 1) return hipErrorInvalidValue;
+  topk_ragged_classify_kernel<<<(unsigned)grid, kTopkRaggedThreads, 0, st>>>(
+      a.offsets, a.nseg, a.num, a.k, a.counts_out, a.list, a.list_cap, a.ctr);
+  return hipGetLastError();
+}
+
+hipError_t launch_topk_ragged_short(int key_size, const TopkRaggedArgs& a, hipStream_t st) {
+  constexpr int64_t kWaveSegs = kTopkRaggedThreads / 64;
+  const int64_t grid = (a.nseg + kWaveSegs - 1) / kWaveSegs;
+  if (grid <= 0 || grid > 0x7fffffff || a.k < 1) return hipErrorInvalidValue;
+#define CALL(KT, U, CZ) \
+  topk_ragged_short_kernel<KT, U><<<(unsigned)grid, kTopkRaggedThreads, 0, st>>>(a)
+  SRS_KEY_DISPATCH(key_size, CALL)
+#undef CALL
+  return hipGetLastError();
+}
+
+hipError_t launch_topk_ragged_long(int key_size, TopkRaggedArgs& a, hipStream_t st) {
+  if (a.k < 1 || a.k > kTopkRowsMaxK || a.num >= (int64_t(1) << 31) || !a.list || a.list_cap < 1)
+    return hipErrorInvalidValue;
+  // the stop rule's capacity, from k alone: segments of up to cap records are
+  // sorted whole; longer ones are refined down to that many slots
+  const int64_t want = std::min<int64_t>(std::max<int64_t>(2 * a.k, kTopkRowsMinCap),
+                                         kTopkRowsStreamCap);
+  int64_t cap = 2;
+  while (cap < want) cap <<= 1;
+  a.cap = (int32_t)cap;
+  const size_t lds = (size_t)cap * ((key_size & 0xff) == 8 ? 12 : 8) +
+                     (sizeof(uint32_t) << kHistMaxBits);
+  int dev = 0, cus = 0;
+  hipError_t err = hipGetDevice(&dev);
+  if (err == hipSuccess) err = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  if (err != hipSuccess) return err;
+  // (a workgroup per listed segment, at most four per CU: the rest of the
+  // list is taken grid-stride; its length is only known on the device)
+  const unsigned grid = (unsigned)std::min<unsigned long long>(a.list_cap, 4ull * (unsigned)std::max(cus, 1));
+#define CALL(KT, U, CZ)                                                                     \
+  do {                                                                                      \
+    auto kern = topk_ragged_long_kernel<KT, U, kTopkRaggedLongThreads>;                     \
+    if (lds > 48 * 1024)                                                                    \
+      err = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                (int)lds);                                                  \
+    if (err == hipSuccess) kern<<<grid, kTopkRaggedLongThreads, lds, st>>>(a);              \
+  } while (0)
+  SRS_KEY_DISPATCH(key_size, CALL)
+#undef CALL
+  return err != hipSuccess ? err : hipGetLastError();
+}
+
+hipError_t launch_topk_ragged_heads(const TopkRaggedArgs& a, hipStream_t st) {
+  constexpr int64_t per = kTopkRaggedThreads * kTopkRaggedItems;
+  const int64_t grid = (a.num + per - 1) / per;
+  if (grid <= 0 || grid > 0x7fffffff || a.k < 1) return hipErrorInvalidValue;
+  topk_ragged_heads_kernel<<<(unsigned)grid, kTopkRaggedThreads, 0, st>>>(a);
+  return hipGetLastError();
+}
+
 }  // namespace srs

@@ -91,6 +91,10 @@ def lib() -> ctypes.CDLL:
                                              vp, vp, vp, vp, vp]
     L.srs_debug_set_sort_ragged_short_max.argtypes = [i32]
     L.srs_debug_last_sort_ragged.argtypes = [ctypes.POINTER(i64)]
+    L.srs_topk_ragged_soa_device.argtypes = [i64, i64, vp, i64, ctypes.c_int, ctypes.c_int, vp,
+                                             i32, vp, vp, vp, vp, vp, vp, vp]
+    L.srs_debug_set_topk_ragged_route.argtypes = [ctypes.c_int]
+    L.srs_debug_last_topk_ragged.argtypes = [ctypes.POINTER(i64)]
     L.srs_fill_synthetic_device.argtypes = [i64, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
                                             vp, i32, vp, vp, vp]
     L.srs_key_histogram_device.argtypes = [i64, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp,
@@ -474,6 +478,56 @@ def sort_ragged_device(keys, *payloads, offsets, up: bool = True, key_kind: int 
     return out + ((idx,) if indices else ())
 
 
+TOPK_RAGGED_KERNELS, TOPK_RAGGED_SORT = 0, 1
+
+
+def topk_ragged_device(keys, *payloads, offsets, k: int, up: bool = True,
+                       key_kind: int | None = None, indices: bool = False, out=None, stream=None):
+    """The first min(k, len) records of every segment [offsets[i],
+    offsets[i+1]) of 1-D device columns in one call
+    (srs_topk_ragged_soa_device): per segment the head of its stable sort by
+    key, equal keys in input order; up=False the largest, descending.
+    `offsets` is sort_ragged_device's: an int64 DEVICE tensor of num_segments
+    + 1 non-decreasing values within [0, len(keys)] on the keys' GPU
+    (TypeError otherwise), read on the device; offsets that decrease or leave
+    the columns raise SrsError. Returns (keys_out, *payloads_out[, indices],
+    counts): the columns of shape (num_segments, k), result j of segment i at
+    [i, j] for j < counts[i] = min(k, len_i); the other slots are not
+    written. New tensors are zero-filled (indices: -1); `out` = (keys_out,
+    *payloads_out), contiguous with at least num_segments * k elements and
+    clear of the inputs, keeps its bytes there. counts is a new int64 tensor
+    of shape (num_segments,)."""
+    import torch
+    cols = (keys,) + payloads
+    _check_columns(keys, cols)
+    if not (isinstance(offsets, torch.Tensor) and offsets.dtype == torch.int64 and
+            offsets.is_cuda and offsets.device == keys.device):
+        raise TypeError("offsets must be an int64 device tensor on the keys' GPU")
+    if not (offsets.dim() == 1 and offsets.is_contiguous()):
+        raise ValueError("offsets must be 1-D and contiguous")
+    n, nseg, k = keys.numel(), max(0, offsets.numel() - 1), max(0, int(k))
+    kind = _torch_kind(keys) if key_kind is None else int(key_kind)
+    dev = keys.device
+    if out is None:
+        out = tuple(torch.zeros((nseg, k), dtype=c.dtype, device=dev) for c in cols)
+    else:
+        out = _out_columns(out, cols, (nseg, k),
+                           "out tensors must be contiguous, on the keys' GPU, of at least "
+                           "num_segments * k elements and of their input's element size")
+    idx = torch.full((nseg, k), -1, dtype=torch.int64, device=dev) if indices else None
+    counts = torch.zeros(nseg, dtype=torch.int64, device=dev)
+    if n == 0 or nseg == 0 or k == 0:  # (an empty tensor has no address to pass)
+        return out + ((idx,) if indices else ()) + (counts,)
+    with _on_device(keys):
+        _check(lib().srs_topk_ragged_soa_device(
+            n, nseg, offsets.data_ptr(), k, kind, int(bool(up)), keys.data_ptr(), len(payloads),
+            _ptr_array([p.data_ptr() for p in payloads]),
+            _size_array([p.element_size() for p in payloads]), out[0].data_ptr(),
+            _ptr_array([o.data_ptr() for o in out[1:]]), None if idx is None else idx.data_ptr(),
+            counts.data_ptr(), _stream_ptr(stream, dev)))
+    return out + ((idx,) if indices else ()) + (counts,)
+
+
 def topk_combined_device(elements, key_kind: int, k: int, up: bool = True, out=None,
                          indices: bool = False, stream=None):
     """topk_device on a DataElement array (srs_topk_aos_device): `elements`
@@ -740,6 +794,23 @@ def debug_last_sort_ragged():
     the last sort_ragged_device on the current device."""
     c = (ctypes.c_int64 * 6)()
     _check(lib().srs_debug_last_sort_ragged(c))
+    return tuple(int(x) for x in c)
+
+
+def debug_set_topk_ragged_route(route: int) -> None:
+    """Route of topk_ragged_device, process-wide
+    (srs_debug_set_topk_ragged_route): -1 the library's rule,
+    TOPK_RAGGED_KERNELS / _SORT force one."""
+    _check(lib().srs_debug_set_topk_ragged_route(int(route)))
+
+
+def debug_last_topk_ragged():
+    """(route, segments the wave kernel owned, segments listed as long, most
+    select passes any segment took, host read-backs, kernel launches or -1 on
+    the sort route) of the last topk_ragged_device on the current device
+    (synchronizes the device)."""
+    c = (ctypes.c_int64 * 6)()
+    _check(lib().srs_debug_last_topk_ragged(c))
     return tuple(int(x) for x in c)
 
 

@@ -1,0 +1,10 @@
+# Builds the device::top_k_ragged test against include/simd_sort/radix_sort.hpp
+# and ../../simd-radix-sort_amd/lib/libsrs_amd.so (hipcc for the HIP runtime
+# headers): make -C tests/cpp -f topk_ragged.mk
+LIBDIR = $(abspath ../../simd-radix-sort_amd/lib)
+.DEFAULT_GOAL := all
+_build/test_topk_ragged: test_topk_ragged.cpp ../../include/simd_sort/radix_sort.hpp ../../include/srs_c_api.h
+	@mkdir -p _build
+	/opt/rocm/bin/hipcc -O2 -std=c++17 -I../../include -o $@ test_topk_ragged.cpp \
+	  -L$(LIBDIR) -lsrs_amd -Wl,-rpath,'$$ORIGIN/../../../simd-radix-sort_amd/lib'
+all: _build/test_topk_ragged
