@@ -391,6 +391,39 @@ void top_k_ragged(void* stream, const SortIndex k, const SortIndex num,
                 "device::top_k_ragged");
 }
 
+// unique: the distinct keys of an array, where each group of equal keys
+// starts and which group every record fell into, in one call
+// (srs_unique_soa_device). With S the stable sort of the input and U its
+// number of runs of equal keys: unique_out[0, U) receives every run's first
+// key (num slots), offsets_out[0, U] every run's start in S and num (num + 1
+// slots; sort_ragged's and top_k_ragged's offsets over the sorted arrays),
+// inverse_out[i] the run number of input record i, keys_sorted_out and every
+// payload's second array S itself, indices_out S's input positions. All but
+// unique_out may be null (keys_sorted_out and the payload outputs together;
+// null only without payloads). Returns U, after one read-back behind the
+// call's kernels.
+template <bool Up = true, typename K, typename... Ps>
+SortIndex unique(void* stream, const SortIndex num, const K* const keys, K* const unique_out,
+                 int64_t* const offsets_out, int64_t* const inverse_out,
+                 K* const keys_sorted_out, int64_t* const indices_out,
+                 std::pair<const Ps*, Ps*>... payloads) {
+  static_assert(detail::key_kind<K>() >= 0, "unsupported key type");
+  static_assert((detail::valid_payload<Ps> && ...), "payload sizes must be 1, 2, 4 or 8");
+  static_assert(sizeof...(Ps) <= SRS_MAX_PAYLOADS, "too many payload arrays");
+  const void* pays[sizeof...(Ps) + 1] = {(const void*)payloads.first..., nullptr};
+  void* pays_out[sizeof...(Ps) + 1] = {(void*)payloads.second..., nullptr};
+  uint32_t sizes[sizeof...(Ps) + 1] = {(uint32_t)sizeof(Ps)..., 0};
+  int64_t num_unique = 0;
+  detail::check(srs_unique_soa_device((int64_t)num, detail::key_kind<K>(), Up ? 1 : 0,
+                                      (const void*)keys, (int32_t)sizeof...(Ps), pays, sizes,
+                                      (void*)keys_sorted_out,
+                                      keys_sorted_out ? pays_out : nullptr, indices_out,
+                                      (void*)unique_out, offsets_out, inverse_out, nullptr,
+                                      &num_unique, stream),
+                "device::unique");
+  return (SortIndex)num_unique;
+}
+
 }  // namespace device
 }  // namespace radix_sort
 }  // namespace simd_sort

@@ -334,6 +334,49 @@ int srs_topk_ragged_soa_device(int64_t num, int64_t num_segments, const int64_t*
                                void* const* payloads_out, int64_t* indices_out,
                                int64_t* counts_out, void* stream);
 
+/* Unique: the distinct keys, where each group of equal keys starts, and
+ * which group every input record fell into, in one call. Let S be the stable
+ * sort of the input by transformed key (srs_sort_soa_device out of place
+ * with num > cmp_sort_threshold: floats in the total order at every size, so
+ * -0.0 and +0.0 are two keys; NaN keys are outside the contract; up == 0
+ * reversed), and U the number of runs of bit-equal keys in S. The inputs are
+ * never written.
+ * unique_out (required, num slots of the key type): slots [0, U) receive the
+ * first key of every run, in S's order; slots from U on are NOT written.
+ * offsets_out (may be NULL, num + 1 int64): slots [0, U] receive every run's
+ * start in S and offsets_out[U] = num, directly usable as the offsets of
+ * srs_sort_ragged_soa_device / srs_topk_ragged_soa_device over the sorted
+ * columns; the counts are its differences. Slots past U are NOT written.
+ * keys_sorted_out / payloads_sorted_out: S itself, num records each; a set,
+ * or both NULL (num_payloads must then be 0, else SRS_ERR_INVALID_ARG; S
+ * lives in the workspace only).
+ * indices_out (may be NULL, num int64): the input position of every record
+ * of S (the argsort); the sort is stable, so indices_out[offsets_out[j]] is
+ * the first occurrence of unique key j in the input.
+ * inverse_out (may be NULL, num int64): inverse_out[i] is the run number,
+ * 0 .. U-1, of input record i: unique_out[inverse_out[i]] is bit-equal to
+ * keys[i].
+ * num_unique_dev (device int64) and num_unique_host (host int64) may each be
+ * NULL; they receive U.
+ * Host waits: with num_unique_host, ONE pinned read-back of U behind all
+ * kernels, and the call returns after it; without it the unique stage (three
+ * launches in stream order: the run tally, the scan of the tile counts, the
+ * write) adds no host wait to what the sort does for its
+ * size.
+ * Checked before any device access: key_kind, payload sizes, NULL or
+ * misaligned pointers (the int64 arrays: 8-byte aligned), num + 1
+ * overflowing, 64 payload columns with an index column (it travels whenever
+ * indices_out or inverse_out is given; SRS_ERR_UNSUPPORTED), and any output
+ * over any input column or over another output. num <= 0 is a no-op that
+ * writes 0 to *num_unique_host if given; num == 1 gives U = 1 and offsets
+ * {0, 1}. No output is accessed outside the slot counts above. SoA only. */
+int srs_unique_soa_device(int64_t num, int key_kind, int up, const void* keys,
+                          int32_t num_payloads, const void* const* payloads,
+                          const uint32_t* payload_sizes, void* keys_sorted_out,
+                          void* const* payloads_sorted_out, int64_t* indices_out,
+                          void* unique_out, int64_t* offsets_out, int64_t* inverse_out,
+                          int64_t* num_unique_dev, int64_t* num_unique_host, void* stream);
+
 /* ---- multi-GPU shard primitives (top-radix-bits partition) --
  * A node-wide sort of one array spread over N GPUs: every rank histograms
  * its keys' top bits (srs_key_histogram_device), the histograms are summed
@@ -655,6 +698,13 @@ int srs_debug_set_topk_ragged_route(int route);
  * 0 on the sort route), info[4] = host read-backs during the call, info[5] =
  * kernel launches queued (-1 on the sort route: not counted). */
 int srs_debug_last_topk_ragged(int64_t* info);
+
+/* What the last unique call on the current device did (host state only: no
+ * synchronization): info[0] = launches the unique stage queued after the
+ * sort (the tally, the scan, the write: 3), info[1] = its host read-backs (0
+ * or 1), info[2] = 1 if an index column travelled through the sort, info[3]
+ * = 1 if S went to workspace columns. */
+int srs_debug_last_unique(int64_t* info);
 
 #ifdef __cplusplus
 }

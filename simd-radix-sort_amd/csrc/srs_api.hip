@@ -604,12 +604,14 @@ Workspace::~Workspace() {
                     &gcount, &tbase, &gbase, &var, &sbase, &tile_seg, &group_seg, &hist, &offs,
                     &gsum, &gofs, &scan_tmp, &totals, &ctr, &prun, &ptile, &btot, &bnt, &btile,
                     &nt_over, &gtile, &gorder, &mid, &midbar, &sel, &selhist, &selcnt, &seldesc,
-                    &rowspass, &sortrowspass, &tkrctr, &tkrlist, &tkrcols};
+                    &rowspass, &sortrowspass, &tkrctr, &tkrlist, &tkrcols, &uniqcols,
+                    &uniqcnt};
   for (DevBuf* b : bufs) free_buf(*b);
   for (auto& t : small_taken) free_buf(t.second);
   if (h_sel) (void)hipHostFree(h_sel);
   if (h_ctr) (void)hipHostFree(h_ctr);
   if (h_tkr) (void)hipHostFree(h_tkr);
+  if (h_uniq) (void)hipHostFree(h_uniq);
   if (h_totals) (void)hipHostFree(h_totals);
   if (h_mid) (void)hipHostFree(h_mid);
   if (side) (void)hipStreamDestroy(side);

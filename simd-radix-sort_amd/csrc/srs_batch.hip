@@ -1,6 +1,6 @@
 // srs_batch.hip — the batched calls on top of the sort driver (srs_driver.h):
-// top-k, row-wise top-k, row-wise sort, ragged sort and ragged top-k, with
-// their out-of-place validation, C entry points and debug hooks.
+// top-k, row-wise top-k, row-wise sort, ragged sort, ragged top-k and unique,
+// with their out-of-place validation, C entry points and debug hooks.
 #include <string.h>
 
 #include <algorithm>
@@ -780,6 +780,156 @@ int topk_ragged_device(const Request& R, int64_t nseg, const int64_t* offsets, i
   return SRS_OK;
 }
 
+// ---------------------------------------------------------------------------
+// unique: the stable sort S of the input (into the caller's
+// sorted columns or workspace columns, with an index column when the argsort
+// or the inverse is asked for), then the run boundaries of S's key column in
+// three launches (run_tally_kernel, launch_excl_scan, run_write_kernel) with
+// nothing read back unless the caller wants U on the host.
+// ---------------------------------------------------------------------------
+// One output array of a unique call, for the overlap tests.
+struct UniqueOut {
+  const void* p;
+  size_t bytes;
+};
+
+// R: the input columns, R.out_cols the caller's sorted columns (sorted: they
+// were given). Everything is checked before the first device access.
+int unique_validate(const Request& R, bool sorted, const int64_t* idx_out, const void* unique_out,
+                    const int64_t* offsets_out, const int64_t* inverse_out,
+                    const int64_t* nu_dev) {
+  const int64_t num = R.num;
+  if (num > (INT64_MAX >> 4)) return fail(SRS_ERR_INVALID_ARG, "num + 1 overflows");
+  if (!R.in_cols[0]) return fail(SRS_ERR_INVALID_ARG, "keys is NULL");
+  if (!unique_out) return fail(SRS_ERR_INVALID_ARG, "unique_out is NULL");
+  for (int c = 0; c < R.ncols; c++) {
+    if (!R.in_cols[c] || (sorted && !R.out_cols[c]))
+      return fail(SRS_ERR_INVALID_ARG, "payload pointer is NULL");
+    SRS_TRY(check_col_alignment(R, c, true));
+  }
+  if ((uintptr_t)unique_out % R.widths[0] != 0)
+    return fail(SRS_ERR_INVALID_ARG, "device arrays must be aligned to their element size");
+  if ((uintptr_t)idx_out % 8 != 0) return fail(SRS_ERR_INVALID_ARG, "indices_out must be 8-byte aligned");
+  if ((uintptr_t)offsets_out % 8 != 0)
+    return fail(SRS_ERR_INVALID_ARG, "offsets_out must be 8-byte aligned");
+  if ((uintptr_t)inverse_out % 8 != 0)
+    return fail(SRS_ERR_INVALID_ARG, "inverse_out must be 8-byte aligned");
+  if ((uintptr_t)nu_dev % 8 != 0)
+    return fail(SRS_ERR_INVALID_ARG, "num_unique_dev must be 8-byte aligned");
+  UniqueOut outs[SRS_MAX_COLS + 5];
+  int no = 0;
+  for (int c = 0; sorted && c < R.ncols; c++) outs[no++] = {R.out_cols[c], (size_t)num * R.widths[c]};
+  outs[no++] = {unique_out, (size_t)num * R.widths[0]};
+  if (idx_out) outs[no++] = {idx_out, (size_t)num * 8};
+  if (offsets_out) outs[no++] = {offsets_out, ((size_t)num + 1) * 8};
+  if (inverse_out) outs[no++] = {inverse_out, (size_t)num * 8};
+  if (nu_dev) outs[no++] = {nu_dev, 8};
+  auto over = [](const void* p, size_t pn, const void* q, size_t qn) {
+    const uintptr_t x = (uintptr_t)p, y = (uintptr_t)q;
+    return x < y + qn && y < x + pn;
+  };
+  for (int o = 0; o < no; o++)
+    for (int c = 0; c < R.ncols; c++)
+      if (over(outs[o].p, outs[o].bytes, R.in_cols[c], (size_t)num * R.widths[c]))
+        return fail(SRS_ERR_INVALID_ARG, "unique outputs must not overlap the inputs");
+  for (int o = 0; o < no; o++)
+    for (int q = o + 1; q < no; q++)
+      if (over(outs[o].p, outs[o].bytes, outs[q].p, outs[q].bytes))
+        return fail(SRS_ERR_INVALID_ARG, "unique outputs must not overlap each other");
+  return SRS_OK;
+}
+
+int unique_device(const Request& R, bool sorted, int64_t* idx_out, void* unique_out,
+                  int64_t* offsets_out, int64_t* inverse_out, int64_t* nu_dev, int64_t* nu_host,
+                  hipStream_t st) {
+  const int64_t n = R.num;
+  const int ks = key_size_of(R.kind);
+  const bool with_idx = idx_out != nullptr || inverse_out != nullptr;
+  WsScope ws;
+  SRS_TRY(ws.begin(st));
+  Workspace* W = ws.W;
+  int64_t* info = W->unique_info;
+  info[0] = info[1] = 0;
+  info[2] = with_idx ? 1 : 0;
+  info[3] = sorted ? 0 : 1;
+
+  // ---- S: the caller's sorted columns, or workspace columns ------------------
+  const size_t key_bytes = sorted ? 0 : align_up((size_t)n * ks, 256);  // (no payloads then)
+  const size_t idx_bytes = with_idx && !idx_out ? (size_t)n * 8 : 0;
+  if (key_bytes + idx_bytes > 0) SRS_TRY(ensure(W->uniqcols, key_bytes + idx_bytes, ws_alloc_mode()));
+  char* dst[SRS_MAX_COLS];
+  for (int c = 0; c < R.ncols; c++) dst[c] = sorted ? (char*)R.out_cols[c] : (char*)W->uniqcols.p;
+  int64_t* idx_col = !with_idx ? nullptr
+                     : idx_out ? idx_out
+                               : (int64_t*)((char*)W->uniqcols.p + key_bytes);
+  const SortDesc kd = init_desc(R.kind, R.up);
+  SelectArgs a;
+  memset(&a, 0, sizeof a);
+  a.stride = (uint32_t)ks;
+  a.n = n;
+  a.all = 1;
+  a.key_bits = kd.key_bits;
+  a.mpos = kd.mpos;
+  a.mneg = kd.mneg;
+  if (!with_idx) {
+    Request F = R;
+    F.thresh = 0;  // (the total order for floats at every size)
+    for (int c = 0; c < R.ncols; c++) F.out_cols[c] = dst[c];
+    SRS_TRY(sort_locked(W, F, st));
+  } else {
+    // the ordered copy adds the index column (as top-k's full route), the
+    // columns are then sorted where they are
+    SRS_TRY(ensure(W->seldesc, sizeof(SortDesc)));
+    SortDesc d = init_desc(R.kind, R.up);
+    for (int c = 0; c < R.ncols; c++) {
+      const uint32_t w = R.widths[c];
+      d.cols[c] = Col{{(char*)R.in_cols[c], dst[c], nullptr, nullptr}, w, {w, w, w, w}};
+    }
+    set_gather_desc(W, d, R.ncols, st);
+    a.keys = (const char*)R.in_cols[0];
+    {
+      TimedScope ts("select_gather", (double)n, st);
+      launch_select_gather(ks, a, (const SortDesc*)W->seldesc.p, nullptr, n, idx_col, st);
+    }
+    HIP_TRY(hipGetLastError());
+    Request S = R;
+    S.thresh = 0;
+    for (int c = 0; c < R.ncols; c++) S.in_cols[c] = S.out_cols[c] = dst[c];
+    S.in_cols[R.ncols] = S.out_cols[R.ncols] = idx_col;
+    S.widths[R.ncols] = 8;
+    S.ncols = R.ncols + 1;
+    SRS_TRY(sort_locked(W, S, st));
+  }
+
+  // ---- the run boundaries of S's key column ----------------------------------
+  const int64_t ntiles = (n + kTile - 1) / kTile;
+  SRS_TRY(ensure(W->uniqcnt, (size_t)(2 * ntiles + scan_temp_elems(ntiles) + 1) * sizeof(uint64_t)));
+  uint64_t* counts = (uint64_t*)W->uniqcnt.p;
+  uint64_t* bases = counts + ntiles;
+  uint64_t* temp = bases + ntiles;
+  uint64_t* total = temp + scan_temp_elems(ntiles);
+  a.keys = dst[0];
+  {
+    TimedScope ts("run_tally", (double)n, st);
+    launch_run_tally(ks, a, counts, st);
+  }
+  launch_excl_scan(counts, bases, ntiles, temp, total, st);
+  {
+    TimedScope ts("run_write", (double)n, st);
+    launch_run_write(ks, a, bases, total, unique_out, offsets_out, idx_col, inverse_out, nu_dev, st);
+  }
+  HIP_TRY(hipGetLastError());
+  info[0] = 3;
+  if (nu_host) {
+    if (!W->h_uniq) HIP_TRY(hipHostMalloc((void**)&W->h_uniq, sizeof(int64_t), hipHostMallocDefault));
+    HIP_TRY(hipMemcpyAsync(W->h_uniq, total, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    SRS_TRY(sync_poll(st));
+    info[1] = 1;
+    *nu_host = *W->h_uniq;
+  }
+  return SRS_OK;
+}
+
 }  // namespace
 }  // namespace srs
 
@@ -897,6 +1047,43 @@ int srs_topk_ragged_soa_device(int64_t num, int64_t num_segments, const int64_t*
   }
   return topk_ragged_device(R, num_segments, offsets, k, indices_out, counts_out,
                             (hipStream_t)stream);
+}
+
+int srs_unique_soa_device(int64_t num, int key_kind, int up, const void* keys,
+                          int32_t num_payloads, const void* const* payloads,
+                          const uint32_t* payload_sizes, void* keys_sorted_out,
+                          void* const* payloads_sorted_out, int64_t* indices_out,
+                          void* unique_out, int64_t* offsets_out, int64_t* inverse_out,
+                          int64_t* num_unique_dev, int64_t* num_unique_host, void* stream) {
+  Request R;
+  SRS_TRY(build_soa(R, num, key_kind, up, 0, (void*)keys, num_payloads, (void* const*)payloads,
+                    payload_sizes, keys_sorted_out, payloads_sorted_out));
+  const bool sorted = keys_sorted_out != nullptr;
+  if (!sorted && num_payloads > 0)
+    return fail(SRS_ERR_INVALID_ARG,
+                "payloads need keys_sorted_out and payloads_sorted_out: num_payloads must be 0 "
+                "without them");
+  if ((indices_out || inverse_out) && num_payloads > SRS_MAX_PAYLOADS - 1)
+    return fail(SRS_ERR_UNSUPPORTED,
+                "indices_out and inverse_out travel as one more payload column: at most 63 "
+                "payload columns with them");
+  if (num <= 0) {
+    if (num_unique_host) *num_unique_host = 0;
+    return SRS_OK;
+  }
+  SRS_TRY(unique_validate(R, sorted, indices_out, unique_out, offsets_out, inverse_out,
+                          num_unique_dev));
+  return unique_device(R, sorted, indices_out, unique_out, offsets_out, inverse_out,
+                       num_unique_dev, num_unique_host, (hipStream_t)stream);
+}
+
+int srs_debug_last_unique(int64_t* info) {
+  if (!info) return fail(SRS_ERR_INVALID_ARG, "info is NULL");
+  Workspace* W = nullptr;
+  WsLock lk;
+  SRS_TRY(acquire_ws(&W, &lk));
+  for (int i = 0; i < 4; i++) info[i] = W->unique_info[i];
+  return SRS_OK;
 }
 
 int srs_debug_set_topk_ragged_route(int route) {

@@ -99,6 +99,12 @@ struct Workspace {
   DevBuf tkrctr, tkrlist, tkrcols;
   TopkRaggedCounters* h_tkr = nullptr;
   int64_t topk_ragged_info[6] = {0, 0, 0, 0, 0, 0};
+  // unique: the sorted columns (and the index column) the caller did not ask
+  // for; the tile counts / bases / scan temp / total; the count's pinned copy;
+  // what the last call did
+  DevBuf uniqcols, uniqcnt;
+  int64_t* h_uniq = nullptr;
+  int64_t unique_info[4] = {0, 0, 0, 0};
   hipStream_t side = nullptr;  // medium sorts: the large local class's stream
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   ListCounters* h_ctr = nullptr;

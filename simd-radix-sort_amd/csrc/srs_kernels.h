@@ -168,6 +168,23 @@ void launch_select_tally(int key_size, const SelectArgs& a, uint64_t* counts, hi
 void launch_select_gather(int key_size, const SelectArgs& a, const SortDesc* d,
                           const uint64_t* tbase, int64_t limit, int64_t* idx_out, hipStream_t st);
 
+// ---- unique --------------------------------------------------
+// The run boundaries of a SORTED key column (a.keys, a.stride, a.n; the
+// prefix fields are unused): record i is a run head when i == 0 or its raw
+// bits differ from record i - 1's.
+// counts: ntiles u64 (ntiles = ceil(n / kTile)), the heads per tile
+void launch_run_tally(int key_size, const SelectArgs& a, uint64_t* counts, hipStream_t st);
+// tbase: the exclusive scan of the tally's counts, *total its total U. Head
+// number j (record i) writes unique_out[j] = its key and offsets_out[j] = i
+// (offsets_out or null; offsets_out[U] = n); with inverse_out, record i's run
+// number goes to inverse_out[idx[i]] (idx: n int64, the records' input
+// positions); num_unique (or null) receives U. No slot >= n (> n of
+// offsets_out) is written.
+void launch_run_write(int key_size, const SelectArgs& a, const uint64_t* tbase,
+                      const uint64_t* total, void* unique_out, int64_t* offsets_out,
+                      const int64_t* idx, int64_t* inverse_out, int64_t* num_unique,
+                      hipStream_t st);
+
 // ---- row-wise top-k ----------------------------------------
 // One workgroup per row, everything decided on the device. Record i of row r
 // of a column of width w is at in + (r * row_stride + i) * w; result j of row

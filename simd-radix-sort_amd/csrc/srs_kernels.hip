@@ -5078,6 +5078,184 @@ void launch_select_gather(int key_size, const SelectArgs& a, const SortDesc* d,
 }
 
 // ---------------------------------------------------------------------------
+// unique (srs_unique_soa_device)
+//
+// The run boundaries of a sorted key column, as the compaction above: record
+// i is a run head when i == 0 or its raw bits differ from record i - 1's (the
+// key transform is a bijection, so equal raw bits are equal keys).
+// run_tally_kernel counts the heads per tile, launch_excl_scan turns the
+// counts into tile bases (its total is U), run_write_kernel writes the heads'
+// keys and positions at base + rank and every record's run number through the
+// index column. Three launches in stream order: no workgroup waits for
+// another.
+// ---------------------------------------------------------------------------
+// select_load<..., true> reads this tile 16 bytes per lane (its own test)
+template <typename KT>
+__device__ __forceinline__ bool select_load_is_vec(const SelectArgs& a, int cnt) {
+  constexpr int KS = (int)sizeof(KT);
+  return kSelItems % (16 / KS) == 0 && cnt == kTile && a.stride == (uint32_t)KS &&
+         ((uintptr_t)a.keys & 15) == 0;
+}
+
+// The keys in front of a wave's groups of consecutive records, in one load
+// per wave: lane l passes the first record of the wave's group l (valid:
+// there is such a group) and receives the key of the record before it (zero
+// for record 0, which is a head whatever this returns).
+template <typename KT, typename U>
+__device__ __forceinline__ U run_wave_pred(const SelectArgs& a, int64_t first, bool valid) {
+  return valid && first > 0 ? (U)gld<KT>(a.keys + (first - 1) * (int64_t)a.stride) : (U)0;
+}
+
+// The key of the record before a lane's: the lane below holds it in `last`,
+// the wave's first lane takes group g's from run_wave_pred's pv.
+template <typename U>
+__device__ __forceinline__ U run_prev(U pv, int g, U last) {
+  const U up = __shfl_up(last, 1, 64);
+  const U p0 = __shfl(pv, g, 64);
+  return lane_id() == 0 ? p0 : up;
+}
+
+// counts[tile] = the run heads among the tile's records.
+template <typename KT, typename U>
+__global__ __launch_bounds__(kSelThreads) void run_tally_kernel(const SelectArgs a,
+                                                                uint64_t* __restrict__ counts) {
+  constexpr int VPL = 16 / (int)sizeof(KT);
+  static_assert(kSelItems % VPL == 0 && kSelItems <= 64, "a lane per group of a wave");
+  __shared__ uint32_t wc[kSelThreads / 64];
+  const int64_t tile = blockIdx.x;
+  const int64_t base = tile * kTile;
+  const int cnt = (int)min((int64_t)kTile, a.n - base);
+  const int t = (int)threadIdx.x, lane = (int)lane_id(), wave0 = t & ~63;
+  const bool vec = select_load_is_vec<KT>(a, cnt);
+  // a wave's groups: the 64 x VPL records of its load j (16 bytes per lane),
+  // or the 64 records of its slot k (element order)
+  const U pv = run_wave_pred<KT, U>(
+      a, vec ? base + ((int64_t)lane * kSelThreads + wave0) * VPL : base + lane * kSelThreads + wave0,
+      vec ? lane < kSelItems / VPL : lane < kSelItems && lane * kSelThreads + wave0 < cnt);
+  U raw[kSelItems];
+  select_load<KT, U, true>(a, base, cnt, raw);
+  uint32_t nh = 0;  // wave-uniform
+  if (vec) {
+    // slot j * VPL + i of thread t is record base + (j * NT + t) * VPL + i
+#pragma unroll
+    for (int j = 0; j < kSelItems / VPL; j++) {
+      U prev = run_prev<U>(pv, j, raw[j * VPL + VPL - 1]);
+      uint32_t mine = (base == 0 && j == 0 && t == 0) ? 1u : (uint32_t)(raw[j * VPL] != prev);
+#pragma unroll
+      for (int i = 1; i < VPL; i++) mine += raw[j * VPL + i] != raw[j * VPL + i - 1];
+      nh += mine;  // (per lane here: summed over the wave below)
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) nh += __shfl_xor(nh, o, 64);
+  } else {
+#pragma unroll
+    for (int k = 0; k < kSelItems; k++) {
+      const int e = k * kSelThreads + t;
+      const U prev = run_prev<U>(pv, k, raw[k]);
+      nh += (uint32_t)__popcll(__ballot(e < cnt && (raw[k] != prev || base + e == 0)));
+    }
+  }
+  if (lane == 0) wc[t >> 6] = nh;
+  __syncthreads();
+  if (t == 0) {
+    uint32_t s = 0;
+    for (int w = 0; w < kSelThreads / 64; w++) s += wc[w];
+    counts[tile] = s;
+  }
+}
+
+// Head i with rank r in tile t: unique_out[tbase[t] + r] = its key and
+// offsets_out[tbase[t] + r] = i; with inverse_out, every record's run number
+// (the heads up to and including it, minus one) goes to inverse_out[idx[i]].
+// The last tile's workgroup writes offsets_out[U] = n and U (= *total, the
+// scan's) to num_unique. No slot >= n (> n of offsets_out) is written,
+// whatever the counts and the index column hold.
+template <typename KT, typename U>
+__global__ __launch_bounds__(kSelThreads) void run_write_kernel(
+    const SelectArgs a, const uint64_t* __restrict__ tbase, const uint64_t* __restrict__ total,
+    int64_t ntiles, KT* __restrict__ unique_out, int64_t* __restrict__ offsets_out,
+    const int64_t* __restrict__ idx, int64_t* __restrict__ inverse_out,
+    int64_t* __restrict__ num_unique) {
+  __shared__ uint32_t wcnt[kSelItems * (kSelThreads / 64)];  // [slot][wave]
+  const int64_t tile = blockIdx.x;
+  const int64_t base = tile * kTile;
+  const int cnt = (int)min((int64_t)kTile, a.n - base);
+  const int t = (int)threadIdx.x, wave = t >> 6;
+  const uint64_t nu = *total;
+  if (tile == ntiles - 1 && t == 0) {
+    if (offsets_out && nu <= (uint64_t)a.n) gst<int64_t>(offsets_out + nu, a.n);
+    if (num_unique) gst<int64_t>(num_unique, (int64_t)nu);
+  }
+  const uint64_t b0 = tbase[tile];
+  // a tile inside one run has no head to write
+  if (!inverse_out && (tile + 1 < ntiles ? tbase[tile + 1] : nu) == b0) return;
+  const int lane = (int)lane_id(), wave0 = t & ~63;
+  const U pv = run_wave_pred<KT, U>(a, base + lane * kSelThreads + wave0,
+                                    lane < kSelItems && lane * kSelThreads + wave0 < cnt);
+  U raw[kSelItems];
+  select_load<KT, U, false>(a, base, cnt, raw);
+  uint32_t heads = 0;  // bit k: slot k is a head
+  uint32_t rk[kSelItems];
+#pragma unroll
+  for (int k = 0; k < kSelItems; k++) {
+    const int e = k * kSelThreads + t;
+    const U prev = run_prev<U>(pv, k, raw[k]);
+    const bool h = e < cnt && (raw[k] != prev || base + e == 0);
+    const uint64_t bh = __ballot(h);
+    rk[k] = popc_below(bh);
+    heads |= (h ? 1u : 0u) << k;
+    if (lane_id() == 0) wcnt[k * 4 + wave] = (uint32_t)__popcll(bh);
+  }
+  __syncthreads();
+  if (t < 64) {  // wave 0: exclusive scan of the 64 (slot, wave) counts
+    const uint32_t v = wcnt[t];
+    uint32_t inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t y = __shfl_up(inc, o, 64);
+      if (t >= o) inc += y;
+    }
+    wcnt[t] = inc - v;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < kSelItems; k++) {
+    const bool h = (heads >> k) & 1u;
+    const uint64_t r = b0 + wcnt[k * 4 + wave] + rk[k];  // heads before this record
+    const int64_t i = base + k * kSelThreads + t;
+    if (h && r < (uint64_t)a.n) {
+      gst<KT>(unique_out + r, (KT)raw[k]);
+      if (offsets_out) gst<int64_t>(offsets_out + r, i);
+    }
+    if (inverse_out && k * kSelThreads + t < cnt) {
+      const uint64_t src = (uint64_t)gld<int64_t>(idx + i);
+      if (src < (uint64_t)a.n) gst<int64_t>(inverse_out + src, (int64_t)(r + (h ? 1 : 0)) - 1);
+    }
+  }
+}
+
+void launch_run_tally(int key_size, const SelectArgs& a, uint64_t* counts, hipStream_t st) {
+  const int64_t ntiles = (a.n + kTile - 1) / kTile;
+  if (ntiles <= 0) return;
+#define CALL(KT, U, CZ) run_tally_kernel<KT, U><<<(unsigned)ntiles, kSelThreads, 0, st>>>(a, counts)
+  SRS_KEY_DISPATCH(key_size, CALL)
+#undef CALL
+}
+
+void launch_run_write(int key_size, const SelectArgs& a, const uint64_t* tbase,
+                      const uint64_t* total, void* unique_out, int64_t* offsets_out,
+                      const int64_t* idx, int64_t* inverse_out, int64_t* num_unique,
+                      hipStream_t st) {
+  const int64_t ntiles = (a.n + kTile - 1) / kTile;
+  if (ntiles <= 0) return;
+#define CALL(KT, U, CZ)                                                                   \
+  run_write_kernel<KT, U><<<(unsigned)ntiles, kSelThreads, 0, st>>>(                      \
+      a, tbase, total, ntiles, (KT*)unique_out, offsets_out, idx, inverse_out, num_unique)
+  SRS_KEY_DISPATCH(key_size, CALL)
+#undef CALL
+}
+
+// ---------------------------------------------------------------------------
 // row-wise top-k (srs_topk_rows_soa_device)
 //
 // The select of §11 with the host taken out: one workgroup owns a row, walks

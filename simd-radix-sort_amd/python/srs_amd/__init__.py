@@ -15,6 +15,7 @@ an exception is raised.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 
@@ -95,6 +96,9 @@ def lib() -> ctypes.CDLL:
                                              i32, vp, vp, vp, vp, vp, vp, vp]
     L.srs_debug_set_topk_ragged_route.argtypes = [ctypes.c_int]
     L.srs_debug_last_topk_ragged.argtypes = [ctypes.POINTER(i64)]
+    L.srs_unique_soa_device.argtypes = [i64, ctypes.c_int, ctypes.c_int, vp, i32, vp, vp, vp, vp,
+                                        vp, vp, vp, vp, vp, vp, vp]
+    L.srs_debug_last_unique.argtypes = [ctypes.POINTER(i64)]
     L.srs_fill_synthetic_device.argtypes = [i64, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
                                             vp, i32, vp, vp, vp]
     L.srs_key_histogram_device.argtypes = [i64, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp,
@@ -526,6 +530,75 @@ def topk_ragged_device(keys, *payloads, offsets, k: int, up: bool = True,
             _ptr_array([o.data_ptr() for o in out[1:]]), None if idx is None else idx.data_ptr(),
             counts.data_ptr(), _stream_ptr(stream, dev)))
     return out + ((idx,) if indices else ()) + (counts,)
+
+
+UniqueResult = collections.namedtuple("UniqueResult",
+                                      "unique sorted offsets counts index inverse")
+
+
+def unique_device(keys, *payloads, up: bool = True, key_kind: int | None = None,
+                  return_sorted: bool = False, return_offsets: bool = False,
+                  return_counts: bool = False, return_index: bool = False,
+                  return_inverse: bool = False, stream=None):
+    """The distinct keys of a 1-D device column in one call
+    (srs_unique_soa_device), in sorted order (floats in the total order: -0.0
+    and +0.0 are two keys; up=False descending). Returns UniqueResult(unique,
+    sorted, offsets, counts, index, inverse); fields not asked for are None.
+    unique: the U distinct keys. sorted (return_sorted): (keys_sorted,
+    *payloads_sorted), the stable sort of the inputs. offsets
+    (return_offsets): int64 of U + 1 values, where each group starts in the
+    sorted columns and len(keys) last, usable as the `offsets` of
+    sort_ragged_device / topk_ragged_device over `sorted`. counts
+    (return_counts): the groups' sizes. index (return_index): the first
+    occurrence of every unique key in the input. inverse (return_inverse):
+    int64 of the input's shape, unique[inverse] == keys. Payloads need
+    return_sorted=True (ValueError). The inputs are not written; the call
+    waits once, for U."""
+    import torch
+    cols = (keys,) + payloads
+    _check_columns(keys, cols)
+    if payloads and not return_sorted:
+        raise ValueError("payloads are only moved with return_sorted=True")
+    kind = _torch_kind(keys) if key_kind is None else int(key_kind)
+    n, dev = keys.numel(), keys.device
+    i64 = dict(dtype=torch.int64, device=dev)
+    want_offs = return_offsets or return_counts or return_index
+    uniq = torch.empty_like(keys)
+    srt = tuple(torch.empty_like(c) for c in cols) if return_sorted else None
+    offs = torch.empty(n + 1, **i64) if want_offs else None
+    idx = torch.empty(n, **i64) if return_index else None
+    inv = torch.empty(keys.shape, **i64) if return_inverse else None
+    nu = ctypes.c_int64(0)
+    if n > 0:  # (an empty tensor has no address to pass)
+        with _on_device(keys):
+            _check(lib().srs_unique_soa_device(
+                n, kind, int(bool(up)), keys.data_ptr(), len(payloads),
+                _ptr_array([p.data_ptr() for p in payloads]) if payloads else None,
+                _size_array([p.element_size() for p in payloads]) if payloads else None,
+                srt[0].data_ptr() if srt else None,
+                _ptr_array([o.data_ptr() for o in srt[1:]]) if srt and payloads else None,
+                None if idx is None else idx.data_ptr(), uniq.data_ptr(),
+                None if offs is None else offs.data_ptr(),
+                None if inv is None else inv.data_ptr(), None, ctypes.byref(nu),
+                _stream_ptr(stream, dev)))
+    elif offs is not None:
+        offs.zero_()
+    u = int(nu.value)
+    if offs is not None:
+        offs = offs[:u + 1]
+    return UniqueResult(
+        unique=uniq[:u], sorted=srt, offsets=offs if return_offsets else None,
+        counts=offs[1:] - offs[:-1] if return_counts else None,
+        index=idx[offs[:-1]] if return_index else None, inverse=inv)
+
+
+def debug_last_unique():
+    """(launches the unique stage queued after the sort, its host read-backs,
+    1 if an index column travelled through the sort, 1 if the sorted columns
+    went to the workspace) of the last unique_device on the current device."""
+    c = (ctypes.c_int64 * 4)()
+    _check(lib().srs_debug_last_unique(c))
+    return tuple(int(x) for x in c)
 
 
 def topk_combined_device(elements, key_kind: int, k: int, up: bool = True, out=None,
