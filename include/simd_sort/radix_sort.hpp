@@ -424,6 +424,44 @@ SortIndex unique(void* stream, const SortIndex num, const K* const keys, K* cons
   return (SortIndex)num_unique;
 }
 
+// search_sorted: the lower and upper bounds of query keys in a sorted array
+// (srs_search_sorted_device), in the sort's key order (Up = false: an array
+// sorted descending; floats in the total order). lower_out[j] receives the
+// number of keys before queries[j], upper_out[j] the number before or equal
+// to it (int64, device; either may be null, not both). flags:
+// SRS_SEARCH_QUERIES_SORTED, a hint. The call does not wait for the device.
+template <bool Up = true, typename K>
+void search_sorted(void* stream, const SortIndex num, const K* const sorted_keys,
+                   const SortIndex num_queries, const K* const queries,
+                   int64_t* const lower_out, int64_t* const upper_out, const int32_t flags = 0) {
+  static_assert(detail::key_kind<K>() >= 0, "unsupported key type");
+  detail::check(srs_search_sorted_device((int64_t)num, detail::key_kind<K>(), Up ? 1 : 0,
+                                         (const void*)sorted_keys, 0, nullptr,
+                                         (int64_t)num_queries, (const void*)queries, nullptr,
+                                         lower_out, upper_out, nullptr, flags, stream),
+                "device::search_sorted");
+}
+
+// The segmented form: offsets is sort_ragged's (num_segments + 1 device
+// values), every segment sorted on its own; queries[j] is searched in segment
+// query_segments[j] (device) and the results are positions inside it. A
+// query with a bad id or a segment with bad offsets receives -1 and is
+// counted in *num_bad_dev (device; may be null), which is not read back.
+template <bool Up = true, typename K>
+void search_sorted(void* stream, const SortIndex num, const K* const sorted_keys,
+                   const SortIndex num_segments, const int64_t* const offsets,
+                   const SortIndex num_queries, const K* const queries,
+                   const int64_t* const query_segments, int64_t* const lower_out,
+                   int64_t* const upper_out, int64_t* const num_bad_dev) {
+  static_assert(detail::key_kind<K>() >= 0, "unsupported key type");
+  detail::check(srs_search_sorted_device((int64_t)num, detail::key_kind<K>(), Up ? 1 : 0,
+                                         (const void*)sorted_keys, (int64_t)num_segments, offsets,
+                                         (int64_t)num_queries, (const void*)queries,
+                                         query_segments, lower_out, upper_out, num_bad_dev, 0,
+                                         stream),
+                "device::search_sorted");
+}
+
 }  // namespace device
 }  // namespace radix_sort
 }  // namespace simd_sort

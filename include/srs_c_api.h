@@ -377,6 +377,77 @@ int srs_unique_soa_device(int64_t num, int key_kind, int up, const void* keys,
                           void* unique_out, int64_t* offsets_out, int64_t* inverse_out,
                           int64_t* num_unique_dev, int64_t* num_unique_host, void* stream);
 
+/* Search-sorted: the lower and upper bounds of query keys in a sorted key
+ * column, in one call. Let T be the key transform of (key_kind, up) (unsigned
+ * keys as they are, signed keys with the sign bit flipped, floats in the
+ * total order so that -0.0 comes before +0.0; up == 0 complements, which
+ * reverses the order). sorted_keys holds num keys of key_kind with T
+ * non-decreasing: what srs_sort_soa_device writes with num >
+ * cmp_sort_threshold, what every total-order call writes (top-k, the
+ * row-wise and the ragged calls), and what unique_out and keys_sorted_out of
+ * srs_unique_soa_device hold. up == 0 therefore means a table sorted
+ * descending. NaN keys are outside the contract, as elsewhere. Neither the
+ * table nor the queries are written.
+ * Flat form (offsets == NULL and query_segments == NULL; num_segments is
+ * ignored): queries holds num_queries keys of the same kind; lower_out[j]
+ * receives the number of table keys t with T(t) < T(q_j), upper_out[j] the
+ * number with T(t) <= T(q_j), both int64. Either output may be NULL, not
+ * both. upper - lower is the number of table keys equal to the query (the
+ * multiplicity of a sort-merge join; non-zero: the key is present); with
+ * unique_out as the table, lower is the group number of a query that is
+ * present (the inverse_out of keys that were not in the unique call).
+ * Segmented form (offsets and query_segments both given, num_segments >= 1;
+ * either one alone is SRS_ERR_INVALID_ARG): offsets is the ragged calls'
+ * array, num_segments + 1 int64 values in device memory, and every segment
+ * [offsets[s], offsets[s + 1]) is sorted on its own, as
+ * srs_sort_ragged_soa_device leaves it. query_segments[j] (device int64,
+ * num_queries entries) names the segment query j is searched in, and the
+ * results are positions inside that segment, 0 .. len. A query is BAD when
+ * its segment id is outside [0, num_segments) or its segment's two offsets
+ * are bad (decreasing, negative, beyond num): it receives -1 in every output
+ * given and is counted in *num_bad_dev (device int64, may be NULL; written
+ * by the call, 0 when there is none). The good queries of the same call are
+ * answered as usual. The kernel tests the id and both offsets itself: no key
+ * outside [0, num) is read whatever the two arrays hold. The call does NOT
+ * read the count back: a lookup has no other host wait and does not gain
+ * one. The flat form writes 0 to *num_bad_dev if it is given.
+ * A table that is not sorted gives unspecified results inside [0, num] ([0,
+ * len] for a segment); nothing outside the columns is accessed.
+ * flags: SRS_SEARCH_QUERIES_SORTED says that the caller believes the queries
+ * are themselves in T order (the output of a sort, for example). It is a
+ * hint for the route only: the kernel then runs on the caller's queries and
+ * narrows every tile of SRS_SEARCH_QUERY_TILE queries to the table range
+ * between the tile's smallest and largest query, so a wrong hint never
+ * changes a result. Without it, many queries against a large table are
+ * first sorted by the call, with an index column, searched in order and
+ * written back through the index (DESIGN.md §17 has the rule).
+ * num_queries <= 0 is a no-op. num <= 0 with queries writes 0 to every
+ * output given; in the segmented form every query is then bad unless its
+ * segment is a valid empty one.
+ * Checked before any device access: key_kind; NULL sorted_keys with num > 0,
+ * NULL queries, both outputs NULL; misaligned pointers (keys to their element
+ * size, the int64 arrays to 8 bytes); num, num_queries * 8 or num_segments +
+ * 1 overflowing; unknown flags bits; offsets without query_segments or the
+ * reverse, num_segments < 1 with them; and every output (num_bad_dev
+ * included) over every input (sorted_keys, queries, offsets, query_segments)
+ * and over every other output.
+ * Host waits: none on the direct route (one kernel, and a memset when
+ * num_bad_dev is given); the sort route has what srs_sort_soa_device has for
+ * num_queries records. */
+#define SRS_SEARCH_QUERIES_SORTED 1 /* flags bit: a hint, see above */
+/* The search kernel's shape, for tests of its edges: queries per workgroup,
+ * the slots of its LDS sample, and the most keys of a table range that is
+ * staged whole. */
+#define SRS_SEARCH_QUERY_TILE 1024
+#define SRS_SEARCH_LDS_SAMPLES 2048
+#define SRS_SEARCH_LDS_RANGE 2047
+int srs_search_sorted_device(int64_t num, int key_kind, int up, const void* sorted_keys,
+                             int64_t num_segments, const int64_t* offsets,
+                             int64_t num_queries, const void* queries,
+                             const int64_t* query_segments, int64_t* lower_out,
+                             int64_t* upper_out, int64_t* num_bad_dev, int32_t flags,
+                             void* stream);
+
 /* ---- multi-GPU shard primitives (top-radix-bits partition) --
  * A node-wide sort of one array spread over N GPUs: every rank histograms
  * its keys' top bits (srs_key_histogram_device), the histograms are summed
@@ -705,6 +776,21 @@ int srs_debug_last_topk_ragged(int64_t* info);
  * or 1), info[2] = 1 if an index column travelled through the sort, info[3]
  * = 1 if S went to workspace columns. */
 int srs_debug_last_unique(int64_t* info);
+
+/* Test hook, process-wide: the route srs_search_sorted_device takes in its
+ * flat form. -1: the library's rule; 0: direct, the kernel runs on the
+ * caller's queries; 1: the queries are sorted first, with an index column
+ * (the hint SRS_SEARCH_QUERIES_SORTED is then ignored). The segmented form
+ * is always route 0 and ignores the hook. Any other value returns
+ * SRS_ERR_INVALID_ARG. Needs no device. */
+int srs_debug_set_search_route(int route);
+
+/* What the last search on the current device did (host state only: no
+ * synchronization): info[0] = the route taken, info[1] = launches of the
+ * search stage (the kernel, and the memset of num_bad_dev when given), info[2]
+ * = host read-backs during the call (0 on route 0; -1 on route 1: the sort's,
+ * not counted), info[3] = 1 if the queries were sorted by the call. */
+int srs_debug_last_search(int64_t* info);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 // srs_batch.hip — the batched calls on top of the sort driver (srs_driver.h):
-// top-k, row-wise top-k, row-wise sort, ragged sort, ragged top-k and unique,
-// with their out-of-place validation, C entry points and debug hooks.
+// top-k, row-wise top-k, row-wise sort, ragged sort, ragged top-k, unique and
+// search-sorted, with their validation, C entry points and debug hooks.
 #include <string.h>
 
 #include <algorithm>
@@ -930,6 +930,175 @@ int unique_device(const Request& R, bool sorted, int64_t* idx_out, void* unique_
   return SRS_OK;
 }
 
+// ---------------------------------------------------------------------------
+// search-sorted: one kernel over the caller's queries (route
+// 0), or over a sorted copy of them that carries their positions, the results
+// written back through that index column (route 1)
+// ---------------------------------------------------------------------------
+static_assert(kSearchTile == SRS_SEARCH_QUERY_TILE && kSearchSamples == SRS_SEARCH_LDS_SAMPLES &&
+                  kSearchFit == SRS_SEARCH_LDS_RANGE,
+              "srs_c_api.h states the search kernel's shape");
+enum { SEARCH_DIRECT = 0, SEARCH_SORT = 1 };
+std::atomic<int> g_search_route{-1};  // srs_debug_set_search_route
+
+// The route of a flat call without the hint, from the measured grid (DESIGN.md
+// §17; tools/search_bench.py): against a table of 2^20 keys the direct kernel
+// wins at every query count (1.1-6x), against 2^22 keys and more sorting the
+// queries first wins from 2^22 queries on (1.05-4.5x at 2^22 .. 2^30 queries,
+// more the larger the table), with 8-byte keys already at 2^20 queries (1.25x;
+// 4-byte keys lose 1.6x there: their sort of 2^20 records has a floor of 0.25
+// ms). Below either bound the direct kernel wins by 1.2-8x.
+constexpr int64_t kSearchSortMinTable = int64_t(1) << 22;
+constexpr int64_t kSearchSortMinQueries = int64_t(1) << 22;
+constexpr int64_t kSearchSortMinQueries8 = int64_t(1) << 20;  // 8-byte keys
+bool search_prefers_sort(int64_t num, int64_t nq, int ks) {
+  return num >= kSearchSortMinTable &&
+         nq >= (ks == 8 ? kSearchSortMinQueries8 : kSearchSortMinQueries);
+}
+
+struct SearchCall {
+  int64_t num, nseg, nq;
+  int kind, up;
+  const void* keys;
+  const int64_t* offsets;
+  const void* queries;
+  const int64_t* qseg;
+  int64_t* lower;
+  int64_t* upper;
+  int64_t* num_bad;
+  int32_t flags;
+};
+
+// Everything is checked before the first device access (nq > 0).
+int search_validate(const SearchCall& C) {
+  const size_t ks = (size_t)key_size_of(C.kind);
+  if (C.num > (INT64_MAX >> 4)) return fail(SRS_ERR_INVALID_ARG, "num overflows");
+  if (C.nq > (INT64_MAX >> 4)) return fail(SRS_ERR_INVALID_ARG, "num_queries * 8 overflows");
+  const bool seg = C.offsets != nullptr;
+  if (seg != (C.qseg != nullptr))
+    return fail(SRS_ERR_INVALID_ARG, "offsets and query_segments must both be set or both NULL");
+  if (seg && C.nseg < 1) return fail(SRS_ERR_INVALID_ARG, "num_segments must be at least 1");
+  if (seg && C.nseg > (INT64_MAX >> 4))
+    return fail(SRS_ERR_INVALID_ARG, "num_segments + 1 overflows");
+  if (C.num > 0 && !C.keys) return fail(SRS_ERR_INVALID_ARG, "sorted_keys is NULL");
+  if (!C.queries) return fail(SRS_ERR_INVALID_ARG, "queries is NULL");
+  if (!C.lower && !C.upper)
+    return fail(SRS_ERR_INVALID_ARG, "lower_out and upper_out are both NULL");
+  if ((uintptr_t)C.keys % ks != 0 || (uintptr_t)C.queries % ks != 0)
+    return fail(SRS_ERR_INVALID_ARG, "device arrays must be aligned to their element size");
+  if ((uintptr_t)C.offsets % 8 != 0) return fail(SRS_ERR_INVALID_ARG, "offsets must be 8-byte aligned");
+  if ((uintptr_t)C.qseg % 8 != 0)
+    return fail(SRS_ERR_INVALID_ARG, "query_segments must be 8-byte aligned");
+  if ((uintptr_t)C.lower % 8 != 0) return fail(SRS_ERR_INVALID_ARG, "lower_out must be 8-byte aligned");
+  if ((uintptr_t)C.upper % 8 != 0) return fail(SRS_ERR_INVALID_ARG, "upper_out must be 8-byte aligned");
+  if ((uintptr_t)C.num_bad % 8 != 0)
+    return fail(SRS_ERR_INVALID_ARG, "num_bad_dev must be 8-byte aligned");
+  const int64_t num = std::max<int64_t>(C.num, 0);
+  const UniqueOut ins[4] = {{C.keys, (size_t)num * ks},
+                            {C.queries, (size_t)C.nq * ks},
+                            {C.offsets, seg ? ((size_t)C.nseg + 1) * 8 : 0},
+                            {C.qseg, seg ? (size_t)C.nq * 8 : 0}};
+  const UniqueOut outs[3] = {{C.lower, C.lower ? (size_t)C.nq * 8 : 0},
+                             {C.upper, C.upper ? (size_t)C.nq * 8 : 0},
+                             {C.num_bad, C.num_bad ? (size_t)8 : 0}};
+  auto over = [](const UniqueOut& p, const UniqueOut& q) {
+    const uintptr_t x = (uintptr_t)p.p, y = (uintptr_t)q.p;
+    return p.bytes && q.bytes && x < y + q.bytes && y < x + p.bytes;
+  };
+  for (const UniqueOut& o : outs)
+    for (const UniqueOut& i : ins)
+      if (over(o, i)) return fail(SRS_ERR_INVALID_ARG, "search outputs must not overlap the inputs");
+  for (int o = 0; o < 3; o++)
+    for (int q = o + 1; q < 3; q++)
+      if (over(outs[o], outs[q]))
+        return fail(SRS_ERR_INVALID_ARG, "search outputs must not overlap each other");
+  return SRS_OK;
+}
+
+int search_device(const SearchCall& C, hipStream_t st) {
+  const int ks = key_size_of(C.kind);
+  const bool seg = C.offsets != nullptr;
+  const int forced = g_search_route.load();
+  const int route = seg                                      ? SEARCH_DIRECT
+                    : forced >= 0                            ? forced
+                    : (C.flags & SRS_SEARCH_QUERIES_SORTED)  ? SEARCH_DIRECT
+                    : search_prefers_sort(C.num, C.nq, ks)   ? SEARCH_SORT
+                                                             : SEARCH_DIRECT;
+  // (the direct route touches no workspace buffer: the lock for the report
+  // below, but no place in the workspace's stream order)
+  WsScope ws;
+  SRS_TRY(route == SEARCH_SORT ? ws.begin(st) : ws.lock());
+  Workspace* W = ws.W;
+  int64_t* info = W->search_info;
+  info[0] = route;
+  info[1] = 0;
+  info[2] = route == SEARCH_SORT ? -1 : 0;
+  info[3] = route == SEARCH_SORT ? 1 : 0;
+
+  const SortDesc kd = init_desc(C.kind, C.up);
+  SearchArgs a;
+  memset(&a, 0, sizeof a);
+  a.keys = (const char*)C.keys;
+  a.num = std::max<int64_t>(C.num, 0);
+  a.queries = (const char*)C.queries;
+  a.nq = C.nq;
+  a.lower = C.lower;
+  a.upper = C.upper;
+  a.offsets = C.offsets;
+  a.qseg = C.qseg;
+  a.nseg = C.nseg;
+  a.num_bad = seg ? C.num_bad : nullptr;
+  a.key_bits = kd.key_bits;
+  a.mpos = kd.mpos;
+  a.mneg = kd.mneg;
+
+  if (route == SEARCH_SORT) {
+    // the ordered copy adds the index column (as unique's), the two columns
+    // are then sorted where they are
+    const size_t key_bytes = align_up((size_t)C.nq * ks, 256);
+    SRS_TRY(ensure(W->searchcols, key_bytes + (size_t)C.nq * 8, ws_alloc_mode()));
+    char* qcopy = (char*)W->searchcols.p;
+    int64_t* idx_col = (int64_t*)(qcopy + key_bytes);
+    SRS_TRY(ensure(W->seldesc, sizeof(SortDesc)));
+    SortDesc d = init_desc(C.kind, C.up);
+    const uint32_t w = (uint32_t)ks;
+    d.cols[0] = Col{{(char*)C.queries, qcopy, nullptr, nullptr}, w, {w, w, w, w}};
+    set_gather_desc(W, d, 1, st);
+    SelectArgs g;
+    memset(&g, 0, sizeof g);
+    g.keys = (const char*)C.queries;
+    g.stride = w;
+    g.n = C.nq;
+    g.all = 1;
+    g.key_bits = kd.key_bits;
+    g.mpos = kd.mpos;
+    g.mneg = kd.mneg;
+    {
+      TimedScope ts("select_gather", (double)C.nq, st);
+      launch_select_gather(ks, g, (const SortDesc*)W->seldesc.p, nullptr, C.nq, idx_col, st);
+    }
+    HIP_TRY(hipGetLastError());
+    Request S;
+    SRS_TRY(build_soa(S, C.nq, C.kind, C.up, 0, qcopy, 0, nullptr, nullptr, nullptr, nullptr));
+    S.in_cols[1] = S.out_cols[1] = idx_col;
+    S.widths[1] = 8;
+    S.ncols = 2;
+    SRS_TRY(sort_locked(W, S, st));
+    a.queries = qcopy;
+    a.idx = idx_col;
+  }
+  if (C.num_bad) {
+    HIP_TRY(hipMemsetAsync(C.num_bad, 0, sizeof(int64_t), st));
+    info[1]++;
+  }
+  {
+    TimedScope ts("search", (double)C.nq, st);
+    HIP_TRY(launch_search(ks, a, st));
+  }
+  info[1]++;
+  return SRS_OK;
+}
+
 }  // namespace
 }  // namespace srs
 
@@ -1083,6 +1252,36 @@ int srs_debug_last_unique(int64_t* info) {
   WsLock lk;
   SRS_TRY(acquire_ws(&W, &lk));
   for (int i = 0; i < 4; i++) info[i] = W->unique_info[i];
+  return SRS_OK;
+}
+
+int srs_search_sorted_device(int64_t num, int key_kind, int up, const void* sorted_keys,
+                             int64_t num_segments, const int64_t* offsets, int64_t num_queries,
+                             const void* queries, const int64_t* query_segments,
+                             int64_t* lower_out, int64_t* upper_out, int64_t* num_bad_dev,
+                             int32_t flags, void* stream) {
+  if (key_size_of(key_kind) == 0) return fail(SRS_ERR_INVALID_ARG, "invalid key_kind");
+  if (flags & ~SRS_SEARCH_QUERIES_SORTED) return fail(SRS_ERR_INVALID_ARG, "unknown flags bits");
+  if (num_queries <= 0) return SRS_OK;
+  const SearchCall C = {num, num_segments, num_queries, key_kind, up ? 1 : 0, sorted_keys, offsets,
+                        queries, query_segments, lower_out, upper_out, num_bad_dev, flags};
+  SRS_TRY(search_validate(C));
+  return search_device(C, (hipStream_t)stream);
+}
+
+int srs_debug_set_search_route(int route) {
+  if (route < -1 || route > SEARCH_SORT)
+    return fail(SRS_ERR_INVALID_ARG, "route must be -1, 0 or 1");
+  g_search_route.store(route);
+  return SRS_OK;
+}
+
+int srs_debug_last_search(int64_t* info) {
+  if (!info) return fail(SRS_ERR_INVALID_ARG, "info is NULL");
+  Workspace* W = nullptr;
+  WsLock lk;
+  SRS_TRY(acquire_ws(&W, &lk));
+  for (int i = 0; i < 4; i++) info[i] = W->search_info[i];
   return SRS_OK;
 }
 

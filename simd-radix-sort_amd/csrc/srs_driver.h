@@ -105,6 +105,10 @@ struct Workspace {
   DevBuf uniqcols, uniqcnt;
   int64_t* h_uniq = nullptr;
   int64_t unique_info[4] = {0, 0, 0, 0};
+  // search-sorted: the sort route's copy of the queries and its index column;
+  // what the last call did
+  DevBuf searchcols;
+  int64_t search_info[4] = {0, 0, 0, 0};
   hipStream_t side = nullptr;  // medium sorts: the large local class's stream
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   ListCounters* h_ctr = nullptr;

@@ -325,4 +325,39 @@ hipError_t launch_topk_ragged_long(int key_size, TopkRaggedArgs& a, hipStream_t 
 // likewise), element-parallel over [0, num).
 hipError_t launch_topk_ragged_heads(const TopkRaggedArgs& a, hipStream_t st);
 
+// ---- search-sorted -------------------------------------------
+// The lower and upper bounds of nq query keys in a dense column of num keys
+// whose transformed keys do not decrease. Query j's results go to slot j of
+// lower / upper (either may be null), or to slot idx[j] when idx is given
+// (the sort route: queries is then the sorted copy, idx its input positions;
+// no slot >= nq is written). Segmented (offsets != null): query j is searched
+// in [offsets[qseg[j]], offsets[qseg[j] + 1]) and its results are positions
+// inside that segment; a query whose id is outside [0, nseg) or whose segment
+// has a bad bound (§14's rule) receives -1 and adds one to *num_bad (or null;
+// zeroed by the caller). No key outside [0, num) is read whatever the table,
+// the offsets and the ids hold, and every result lies in [0, num] ([0, len]).
+struct SearchArgs {
+  const char* keys;
+  int64_t num;
+  const char* queries;
+  int64_t nq;
+  const int64_t* idx;      // or null
+  int64_t* lower;          // or null
+  int64_t* upper;          // or null
+  const int64_t* offsets;  // or null: the flat form
+  const int64_t* qseg;
+  int64_t nseg;
+  int64_t* num_bad;        // or null
+  int32_t key_bits;
+  uint64_t mpos, mneg;     // SortDesc's key transform
+};
+constexpr int kSearchThreads = 256;
+constexpr int kSearchItems = 4;
+constexpr int kSearchTile = kSearchThreads * kSearchItems;  // queries per workgroup
+// the LDS sample's slots; a tile whose table range has at most kSearchFit keys
+// stages the range itself
+constexpr int kSearchSamples = 2048;
+constexpr int kSearchFit = kSearchSamples - 1;
+hipError_t launch_search(int key_size, const SearchArgs& a, hipStream_t st);
+
 }  // namespace srs

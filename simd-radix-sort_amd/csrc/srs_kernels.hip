@@ -6323,4 +6323,266 @@ hipError_t launch_topk_ragged_heads(const TopkRaggedArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// search-sorted (srs_search_sorted_device)
+//
+// One workgroup takes a tile of kSearchTile consecutive queries, kSearchItems
+// per lane. Flat form: the workgroup reduces the tile's smallest and largest
+// transformed query, finds the table range [lb(min), ub(max)) every result of
+// the tile lies in (a 256-ary search, all lanes probing at once), stages up
+// to kSearchSamples keys of that range in LDS at positions that are multiples
+// of a power-of-two step (the range itself when it has at most kSearchFit
+// keys; tiles with similar ranges read the same lines), places every query
+// among the samples with LDS reads only and finishes it in the slice between
+// two samples, a lane's queries interleaved so that kSearchItems loads are in
+// flight. Segmented form: every query starts from its own segment's bounds,
+// which the kernel tests itself. No workgroup waits for another; the only
+// atomic is the bad-query count, added once per workgroup.
+// ---------------------------------------------------------------------------
+static_assert(kSearchItems * kSearchThreads == kSearchTile, "search block shape");
+static_assert((kSearchSamples & (kSearchSamples - 1)) == 0 && kSearchFit == kSearchSamples - 1,
+              "search_kernel's sample walk");
+
+template <typename U>
+__device__ __forceinline__ Xform<U> search_xform(const SearchArgs& a) {
+  Xform<U> xf;
+  xf.mpos = (U)a.mpos;
+  xf.cdiff = (U)(a.mpos ^ a.mneg);
+  xf.negzero = 0;
+  xf.sbit = a.key_bits - 1;
+  xf.canon = false;
+  return xf;
+}
+
+// Every item's a[k] moves to a[k] + the keys t of [a[k], b[k]) with T(t) <
+// x[k] (LE: <=), for a column sorted inside every item's range; a[k] stays
+// inside [a[k], b[k]] whatever the column holds. g0 == 0: bisection; g0 == 1:
+// the probes first gallop from a[k] (1, 2, 4, ... apart) and bisect once one
+// fails, for ranges whose answer is expected near their start. The items'
+// loads are issued together; an item that is done reads key 0.
+template <typename KT, typename U, bool LE>
+__device__ __forceinline__ void search_slices(const char* keys, int64_t num, const Xform<U>& xf,
+                                              const U (&x)[kSearchItems],
+                                              int64_t (&a)[kSearchItems],
+                                              int64_t (&b)[kSearchItems], int64_t g0) {
+  if (num <= 0) return;
+  int64_t g[kSearchItems];
+  bool more = false;
+#pragma unroll
+  for (int k = 0; k < kSearchItems; k++) {
+    g[k] = g0;
+    more |= a[k] < b[k];
+  }
+  while (more) {
+    int64_t p[kSearchItems];
+    U v[kSearchItems];
+#pragma unroll
+    for (int k = 0; k < kSearchItems; k++) {
+      const int64_t pk = g[k] ? min(a[k] + g[k] - 1, b[k] - 1) : a[k] + ((b[k] - a[k]) >> 1);
+      p[k] = a[k] < b[k] ? pk : 0;
+    }
+#pragma unroll
+    for (int k = 0; k < kSearchItems; k++) v[k] = (U)gld<KT>(keys + p[k] * (int64_t)sizeof(KT));
+    more = false;
+#pragma unroll
+    for (int k = 0; k < kSearchItems; k++) {
+      if (a[k] < b[k]) {
+        const U u = xf(v[k]);
+        if (LE ? u <= x[k] : u < x[k]) {
+          a[k] = p[k] + 1;
+          g[k] += g[k];
+        } else {
+          b[k] = p[k];
+          g[k] = 0;
+        }
+      }
+      more |= a[k] < b[k];
+    }
+  }
+}
+
+template <typename KT, typename U, bool SEG>
+__global__ __launch_bounds__(kSearchThreads) void search_kernel(const SearchArgs a) {
+  constexpr int KS = (int)sizeof(KT);
+  constexpr int NW = kSearchThreads / 64;
+  __shared__ U smp[SEG ? 1 : kSearchSamples];
+  __shared__ U red[2][NW];
+  __shared__ uint32_t cw[2][2][NW];  // [iteration parity][search][wave]
+  const int t = (int)threadIdx.x, wave = t >> 6;
+  const int64_t base = (int64_t)blockIdx.x * kSearchTile;
+  const int cnt = (int)min((int64_t)kSearchTile, a.nq - base);
+  const Xform<U> xf = search_xform<U>(a);
+  U x[kSearchItems];
+  bool ok[kSearchItems];
+#pragma unroll
+  for (int k = 0; k < kSearchItems; k++) {
+    const int e = k * kSearchThreads + t;
+    ok[k] = e < cnt;
+    x[k] = ok[k] ? xf((U)gld<KT>(a.queries + (base + e) * KS)) : (U)0;
+  }
+  int64_t lb[kSearchItems], ub[kSearchItems], end[kSearchItems];
+  int64_t off[kSearchItems];  // what a result is relative to (SEG); < 0: a bad query
+
+  if constexpr (SEG) {
+    uint32_t nbad = 0;
+#pragma unroll
+    for (int k = 0; k < kSearchItems; k++) {
+      const int64_t j = base + k * kSearchThreads + t;
+      const int64_t s = ok[k] ? gld<int64_t>(a.qseg + j) : -1;
+      bool good = ok[k] && (uint64_t)s < (uint64_t)a.nseg;
+      const int64_t o0 = good ? gld<int64_t>(a.offsets + s) : 0;
+      const int64_t o1 = good ? gld<int64_t>(a.offsets + s + 1) : 0;
+      good = good && o0 >= 0 && o1 >= o0 && o1 <= a.num;
+      nbad += (uint32_t)__popcll(__ballot(ok[k] && !good));
+      off[k] = good ? o0 : -1;
+      lb[k] = good ? o0 : 0;
+      end[k] = good ? o1 : 0;
+    }
+    if (a.num_bad) {
+      if (lane_id() == 0) cw[0][0][wave] = nbad;
+      __syncthreads();
+      if (t == 0) {
+        uint32_t s = 0;
+        for (int w = 0; w < NW; w++) s += cw[0][0][w];
+        if (s) atomicAdd((unsigned long long*)a.num_bad, (unsigned long long)s);
+      }
+    }
+    int64_t b[kSearchItems];
+#pragma unroll
+    for (int k = 0; k < kSearchItems; k++) b[k] = end[k];
+    search_slices<KT, U, false>(a.keys, a.num, xf, x, lb, b, 0);
+    if (a.upper) {
+#pragma unroll
+      for (int k = 0; k < kSearchItems; k++) ub[k] = lb[k];
+      search_slices<KT, U, true>(a.keys, a.num, xf, x, ub, end, 1);
+    }
+  } else {
+    // ---- the tile's smallest and largest query ----------------------------
+    U qmin = ~(U)0, qmax = 0;
+#pragma unroll
+    for (int k = 0; k < kSearchItems; k++) {
+      qmin = ok[k] && x[k] < qmin ? x[k] : qmin;
+      qmax = ok[k] && x[k] > qmax ? x[k] : qmax;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      const U m = __shfl_xor(qmin, o, 64), M = __shfl_xor(qmax, o, 64);
+      qmin = m < qmin ? m : qmin;
+      qmax = M > qmax ? M : qmax;
+    }
+    if (lane_id() == 0) {
+      red[0][wave] = qmin;
+      red[1][wave] = qmax;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < NW; w++) {
+      qmin = red[0][w] < qmin ? red[0][w] : qmin;
+      qmax = red[1][w] > qmax ? red[1][w] : qmax;
+    }
+    // ---- [lb(min), ub(max)): two 256-ary searches, every lane probing -------
+    // (lo, hi and the counts are the same in every lane: uniform control flow)
+    int64_t lo[2] = {0, 0}, hi[2] = {a.num, a.num};
+    for (int it = 0; lo[0] < hi[0] || lo[1] < hi[1]; it++) {
+      int64_t step[2];
+#pragma unroll
+      for (int s = 0; s < 2; s++) {
+        const int64_t len = hi[s] - lo[s];
+        step[s] = (len + kSearchThreads - 1) / kSearchThreads;
+        const int64_t pos = lo[s] + t * step[s];
+        bool pred = false;
+        if (len > 0 && pos < hi[s]) {
+          const U u = xf((U)gld<KT>(a.keys + pos * KS));
+          pred = s == 0 ? u < qmin : u <= qmax;
+        }
+        const uint32_t c = (uint32_t)__popcll(__ballot(pred));
+        if (lane_id() == 0) cw[it & 1][s][wave] = c;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int s = 0; s < 2; s++) {
+        if (lo[s] >= hi[s]) continue;
+        uint32_t c = 0;
+#pragma unroll
+        for (int w = 0; w < NW; w++) c += cw[it & 1][s][w];
+        if (c == 0) {
+          hi[s] = lo[s];
+        } else {
+          const int64_t nlo = lo[s] + (int64_t)(c - 1) * step[s] + 1;
+          hi[s] = min(hi[s], lo[s] + (int64_t)c * step[s]);
+          lo[s] = nlo;
+        }
+      }
+    }
+    const int64_t rlo = lo[0], rhi = max(lo[1], lo[0]);
+    // ---- the range's samples: multiples of 2^lg inside it --------------------
+    int lg = 0;
+    while (((int64_t)kSearchFit << lg) < rhi - rlo) lg++;
+    const int64_t first = ((rlo + ((int64_t)1 << lg) - 1) >> lg) << lg;
+    const int ns = first < rhi ? (int)(((rhi - 1 - first) >> lg) + 1) : 0;  // <= kSearchFit
+    for (int i = t; i < ns; i += kSearchThreads)
+      smp[i] = xf((U)gld<KT>(a.keys + (first + ((int64_t)i << lg)) * KS));
+    __syncthreads();
+    // ---- every query among the samples, then inside its slice ----------------
+    int64_t b[kSearchItems];
+#pragma unroll
+    for (int k = 0; k < kSearchItems; k++) {
+      uint32_t c = 0;
+#pragma unroll
+      for (uint32_t w = kSearchSamples >> 1; w; w >>= 1) {
+        const uint32_t p = c + w;
+        if (p <= (uint32_t)ns && smp[p - 1] < x[k]) c = p;
+      }
+      lb[k] = c ? first + ((int64_t)(c - 1) << lg) + 1 : rlo;
+      b[k] = c < (uint32_t)ns ? first + ((int64_t)c << lg) : rhi;
+      if (!ok[k]) lb[k] = b[k] = 0;
+      off[k] = 0;
+    }
+    search_slices<KT, U, false>(a.keys, a.num, xf, x, lb, b, 0);
+    if (a.upper) {
+#pragma unroll
+      for (int k = 0; k < kSearchItems; k++) {
+        uint32_t c = 0;
+#pragma unroll
+        for (uint32_t w = kSearchSamples >> 1; w; w >>= 1) {
+          const uint32_t p = c + w;
+          if (p <= (uint32_t)ns && smp[p - 1] <= x[k]) c = p;
+        }
+        // (upper starts from lower: ub >= lb)
+        const int64_t a2 = c ? first + ((int64_t)(c - 1) << lg) + 1 : rlo;
+        const int64_t b2 = c < (uint32_t)ns ? first + ((int64_t)c << lg) : rhi;
+        ub[k] = max(a2, lb[k]);
+        end[k] = max(b2, ub[k]);
+        if (!ok[k]) ub[k] = end[k] = 0;
+      }
+      search_slices<KT, U, true>(a.keys, a.num, xf, x, ub, end, 1);
+    }
+  }
+
+  // ---- results: to slot j, or through the index column ------------------------
+#pragma unroll
+  for (int k = 0; k < kSearchItems; k++) {
+    if (!ok[k]) continue;
+    const int64_t j = base + k * kSearchThreads + t;
+    const int64_t dst = a.idx ? gld<int64_t>(a.idx + j) : j;
+    if ((uint64_t)dst >= (uint64_t)a.nq) continue;
+    const bool bad = off[k] < 0;
+    if (a.lower) gst<int64_t>(a.lower + dst, bad ? -1 : lb[k] - off[k]);
+    if (a.upper) gst<int64_t>(a.upper + dst, bad ? -1 : ub[k] - off[k]);
+  }
+}
+
+hipError_t launch_search(int key_size, const SearchArgs& a, hipStream_t st) {
+  const int64_t grid = (a.nq + kSearchTile - 1) / kSearchTile;
+  if (grid <= 0 || grid > 0x7fffffff) return hipErrorInvalidValue;
+#define CALL(KT, U, CZ)                                                                \
+  do {                                                                                 \
+    if (a.offsets) search_kernel<KT, U, true><<<(unsigned)grid, kSearchThreads, 0, st>>>(a); \
+    else search_kernel<KT, U, false><<<(unsigned)grid, kSearchThreads, 0, st>>>(a);    \
+  } while (0)
+  SRS_KEY_DISPATCH(key_size, CALL)
+#undef CALL
+  return hipGetLastError();
+}
+
 }  // namespace srs

@@ -99,6 +99,10 @@ def lib() -> ctypes.CDLL:
     L.srs_unique_soa_device.argtypes = [i64, ctypes.c_int, ctypes.c_int, vp, i32, vp, vp, vp, vp,
                                         vp, vp, vp, vp, vp, vp, vp]
     L.srs_debug_last_unique.argtypes = [ctypes.POINTER(i64)]
+    L.srs_search_sorted_device.argtypes = [i64, ctypes.c_int, ctypes.c_int, vp, i64, vp, i64, vp,
+                                           vp, vp, vp, vp, i32, vp]
+    L.srs_debug_set_search_route.argtypes = [ctypes.c_int]
+    L.srs_debug_last_search.argtypes = [ctypes.POINTER(i64)]
     L.srs_fill_synthetic_device.argtypes = [i64, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
                                             vp, i32, vp, vp, vp]
     L.srs_key_histogram_device.argtypes = [i64, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp,
@@ -598,6 +602,107 @@ def debug_last_unique():
     went to the workspace) of the last unique_device on the current device."""
     c = (ctypes.c_int64 * 4)()
     _check(lib().srs_debug_last_unique(c))
+    return tuple(int(x) for x in c)
+
+
+SEARCH_QUERIES_SORTED = 1  # srs_c_api.h: SRS_SEARCH_QUERIES_SORTED
+SEARCH_DIRECT, SEARCH_SORT = 0, 1
+# the search kernel's shape (srs_c_api.h): queries per workgroup, the slots of
+# its LDS sample, the most keys of a table range that is staged whole
+SEARCH_QUERY_TILE, SEARCH_LDS_SAMPLES, SEARCH_LDS_RANGE = 1024, 2048, 2047
+
+
+def searchsorted_device(sorted_keys, queries, *, side: str = "left", up: bool = True,
+                        key_kind: int | None = None, offsets=None, query_segments=None,
+                        queries_sorted: bool = False, out=None, stream=None):
+    """Where query keys fall in a sorted 1-D device column
+    (srs_search_sorted_device), in the library's key order: floats in the
+    total order (-0.0 before +0.0), up=False for a table sorted descending,
+    key_kind for uint64 keys held as int64. `sorted_keys` is what sort_device,
+    the row-wise and ragged calls or unique_device (`unique`, `sorted`) wrote;
+    `queries` a contiguous device tensor of any shape with the table's dtype
+    (TypeError otherwise). side="left": the number of table keys before the
+    query; "right": the number of keys before or equal to it; "both": (lower,
+    upper), whose difference is the number of matches. The results are int64
+    tensors of the queries' shape (`out`: a contiguous int64 tensor of at
+    least that many elements, or a pair of them for "both"). With
+    unique_device(keys).unique as the table, "left" is the group number of
+    every query that is present.
+    Segmented: `offsets` (the ragged calls' int64 DEVICE tensor of
+    num_segments + 1 values) and `query_segments` (int64 device tensor of the
+    queries' shape) search every query in its own segment; the results are
+    positions inside the segment. A query with a segment id outside [0,
+    num_segments) or a segment with bad offsets receives -1, and a `bad` count
+    tensor (device, 1 element, not read here) is returned last.
+    queries_sorted=True is a hint that the queries are already in key order;
+    a wrong hint costs time, never a result."""
+    import torch
+    if side not in ("left", "right", "both"):
+        raise ValueError('side must be "left", "right" or "both"')
+    if not (isinstance(sorted_keys, torch.Tensor) and sorted_keys.is_cuda and
+            sorted_keys.dim() == 1 and sorted_keys.is_contiguous()):
+        raise ValueError("sorted_keys must be a 1-D contiguous device tensor")
+    if not (isinstance(queries, torch.Tensor) and queries.dtype == sorted_keys.dtype):
+        raise TypeError("queries must be a tensor of the table's dtype")
+    dev = sorted_keys.device
+    if not (queries.is_cuda and queries.device == dev and queries.is_contiguous()):
+        raise ValueError("queries must be a contiguous device tensor on the table's GPU")
+    seg = offsets is not None or query_segments is not None
+    if seg:
+        for name, t in (("offsets", offsets), ("query_segments", query_segments)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.int64 and t.is_cuda and
+                    t.device == dev):
+                raise TypeError(f"{name} must be an int64 device tensor on the keys' GPU")
+        if not (offsets.dim() == 1 and offsets.is_contiguous() and offsets.numel() >= 2):
+            raise ValueError("offsets must be 1-D, contiguous and hold num_segments + 1 >= 2 values")
+        if not (query_segments.is_contiguous() and query_segments.numel() == queries.numel()):
+            raise ValueError("query_segments must be contiguous and of the queries' shape")
+    kind = _torch_kind(sorted_keys) if key_kind is None else int(key_kind)
+    n, nq = sorted_keys.numel(), queries.numel()
+    nres = 2 if side == "both" else 1
+    if out is None:
+        res = tuple(torch.empty(queries.shape, dtype=torch.int64, device=dev) for _ in range(nres))
+    else:
+        res = tuple(out) if side == "both" else (out,)
+        if len(res) != nres:
+            raise ValueError('out must be one tensor, or (lower, upper) for side="both"')
+        for o in res:
+            if not (isinstance(o, torch.Tensor) and o.dtype == torch.int64 and o.is_cuda and
+                    o.device == dev and o.is_contiguous() and o.numel() >= nq):
+                raise ValueError("out tensors must be contiguous int64 device tensors on the "
+                                 "table's GPU with at least as many elements as queries")
+    lower = res[0] if side != "right" else None
+    upper = res[-1] if side != "left" else None
+    bad = torch.zeros(1, dtype=torch.int64, device=dev) if seg else None
+    if nq > 0:  # (an empty tensor has no address to pass)
+        with _on_device(sorted_keys):
+            _check(lib().srs_search_sorted_device(
+                n, kind, int(bool(up)), sorted_keys.data_ptr() if n > 0 else None,
+                offsets.numel() - 1 if seg else 0, offsets.data_ptr() if seg else None, nq,
+                queries.data_ptr(), query_segments.data_ptr() if seg else None,
+                None if lower is None else lower.data_ptr(),
+                None if upper is None else upper.data_ptr(),
+                None if bad is None else bad.data_ptr(),
+                SEARCH_QUERIES_SORTED if queries_sorted else 0, _stream_ptr(stream, dev)))
+    ret = res[0] if nres == 1 else res
+    if seg:
+        return (ret, bad) if nres == 1 else res + (bad,)
+    return ret
+
+
+def debug_set_search_route(route: int) -> None:
+    """Test hook (srs_debug_set_search_route): -1 the library's rule, 0 the
+    kernel on the caller's queries, 1 sort the queries first. The segmented
+    form ignores it."""
+    _check(lib().srs_debug_set_search_route(int(route)))
+
+
+def debug_last_search():
+    """(route taken, launches of the search stage, host read-backs or -1 on
+    the sort route, 1 if the call sorted the queries) of the last
+    searchsorted_device on the current device."""
+    c = (ctypes.c_int64 * 4)()
+    _check(lib().srs_debug_last_search(c))
     return tuple(int(x) for x in c)
 
 
