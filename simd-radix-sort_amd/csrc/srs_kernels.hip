@@ -4797,14 +4797,18 @@ static_assert(kSelItems * kSelThreads == kTile, "select block shape");
 static_assert(kSelThreads == 256 && kSelItems == 16, "the gather scans 16 x 4 wave counts in one wave");
 
 template <typename U>
-__device__ __forceinline__ Xform<U> select_xform(const SelectArgs& a) {
+__device__ __forceinline__ Xform<U> select_xform(int key_bits, uint64_t mpos, uint64_t mneg) {
   Xform<U> xf;
-  xf.mpos = (U)a.mpos;
-  xf.cdiff = (U)(a.mpos ^ a.mneg);
+  xf.mpos = (U)mpos;
+  xf.cdiff = (U)(mpos ^ mneg);
   xf.negzero = 0;
-  xf.sbit = a.key_bits - 1;
+  xf.sbit = key_bits - 1;
   xf.canon = false;
   return xf;
+}
+template <typename U>
+__device__ __forceinline__ Xform<U> select_xform(const SelectArgs& a) {
+  return select_xform<U>(a.key_bits, a.mpos, a.mneg);
 }
 
 // The tile's keys, ITEMS per thread of NT. A full tile of a dense, 16-byte
@@ -5306,30 +5310,48 @@ __device__ __forceinline__ void rows_bitonic(U* sk, uint32_t* si, uint32_t p2, u
   }
 }
 
-// The first kk records of a row from the sorted positions si[0 .. kk): every
-// column read by position (payload bytes for the selected records only).
+// The first c records of a row or segment of n records from the sorted
+// positions si[0 .. c): result j, at record out0 + j of the outputs, is input
+// record in0 + si[j]. Every column is read by position (payload bytes for
+// the selected records only).
 template <typename KT>
-__device__ __forceinline__ void rows_write(const TopkRowsArgs& A, int64_t row, const uint32_t* si,
-                                           uint32_t t, uint32_t nt) {
+__device__ __forceinline__ void write_by_position(const TopkRowsCol* col, int ncols,
+                                                  int64_t* idx_out, int64_t in0, int64_t out0,
+                                                  uint32_t n, uint32_t c, const uint32_t* si,
+                                                  uint32_t t, uint32_t nt) {
   constexpr int KS = (int)sizeof(KT);
-  const uint32_t n = (uint32_t)A.row_len, kk = (uint32_t)A.kk;
-  const int64_t in0 = row * A.row_stride, out0 = row * (int64_t)kk;
-  for (uint32_t j = t; j < kk; j += nt) {
+  for (uint32_t j = t; j < c; j += nt) {
     const uint32_t e = si[j];
-    if (e >= n) continue;  // (a padding slot: never inside the first kk)
-    stw<KS>(A.col[0].out + (out0 + j) * KS, (uint64_t)gld<KT>(A.col[0].in + (in0 + e) * KS));
-    if (A.idx_out) gst<int64_t>(A.idx_out + out0 + j, (int64_t)e);
+    if (e >= n) continue;  // (a padding slot: never inside the first c)
+    stw<KS>(col[0].out + (out0 + j) * KS, (uint64_t)gld<KT>(col[0].in + (in0 + e) * KS));
+    if (idx_out) gst<int64_t>(idx_out + out0 + j, (int64_t)e);
   }
-  for (int c = 1; c < A.ncols; c++) {
-    const TopkRowsCol& C = A.col[c];
+  for (int q = 1; q < ncols; q++) {
+    const TopkRowsCol& C = col[q];
     with_width(C.width, [&](auto W_) {
       constexpr int W = decltype(W_)::value;
-      for (uint32_t j = t; j < kk; j += nt) {
+      for (uint32_t j = t; j < c; j += nt) {
         const uint32_t e = si[j];
         if (e < n) stw<W>(C.out + (out0 + j) * W, ldw<W>(C.in + (in0 + e) * W));
       }
     });
   }
+}
+
+// One WAVE sorts the n records whose keys start at `keys` (dense): the
+// (transformed key, position) pairs into the wave's slab, padded to p2 (a
+// power of two >= n) pairs, and the network over them. No workgroup barrier.
+template <typename KT, typename U>
+__device__ __forceinline__ void wave_sort_segment(const char* keys, uint32_t n, uint32_t p2, U* sk,
+                                                  uint32_t* si, const Xform<U>& xf, uint32_t lane) {
+  constexpr int KS = (int)sizeof(KT);
+  for (uint32_t e = lane; e < p2; e += 64) {
+    const bool ok = e < n;
+    sk[e] = ok ? xf((U)gld<KT>(keys + (int64_t)e * KS)) : (U)~(U)0;
+    si[e] = ok ? e : 0xffffffffu;
+  }
+  wave_lds_sync();
+  rows_bitonic(sk, si, p2, lane, 64u, [] { wave_lds_sync(); });
 }
 
 // Rows of at most kRowsWaveMax records: one WAVE per row, kRowsWaveThreads /
@@ -5347,25 +5369,27 @@ __global__ __launch_bounds__(kRowsWaveThreads) void topk_rows_wave_kernel(const 
   const uint32_t n = (uint32_t)A.row_len, p2 = (uint32_t)A.cap;
   U* const sk = (U*)topk_rows_lds + wave * p2;
   uint32_t* const si = (uint32_t*)((U*)topk_rows_lds + WPB * p2) + wave * p2;
-  SelectArgs a;
-  a.key_bits = A.key_bits;
-  a.mpos = A.mpos;
-  a.mneg = A.mneg;
-  const Xform<U> xf = select_xform<U>(a);
-  const char* keys = A.col[0].in + row * A.row_stride * KS;
-  for (uint32_t e = lane; e < p2; e += 64) {
-    const bool ok = e < n;
-    sk[e] = ok ? xf((U)gld<KT>(keys + (int64_t)e * KS)) : (U)~(U)0;
-    si[e] = ok ? e : 0xffffffffu;
-  }
-  wave_lds_sync();
-  rows_bitonic(sk, si, p2, lane, 64u, [] { wave_lds_sync(); });
-  rows_write<KT>(A, row, si, lane, 64u);
+  wave_sort_segment<KT, U>(A.col[0].in + row * A.row_stride * KS, n, p2, sk, si,
+                           select_xform<U>(A.key_bits, A.mpos, A.mneg), lane);
+  write_by_position<KT>(A.col, A.ncols, A.idx_out, row * A.row_stride, row * A.kk, n,
+                        (uint32_t)A.kk, si, lane, 64u);
 }
 
+// The workgroup select and sort (the walk described above; every row or
+// segment kernel calls this one copy): the selected records of the key
+// column a (keys / stride / n / key_bits / mpos / mneg), at least its first
+// kk, sorted by (key, position) into sk / si[0 .. p2), p2 the power of two >=
+// their number (padding slots hold position 0xffffffff and sort last). The
+// number of histogram passes is returned. sk / si: cap slots each; h: the
+// 2^kHistMaxBits bins (select == false: not allocated, a.n <= cap, no pass is
+// made). STREAM == false: a.n <= NT * kRowItems, the column is held in
+// registers. Called by all NT threads with the same arguments, and
+// everything else a trip count depends on is read from LDS behind a barrier:
+// every condition around a barrier is uniform over the workgroup. The caller
+// puts a barrier between its last read of si and the next call.
 template <typename KT, typename U, int NT, bool STREAM>
-__global__ __launch_bounds__(NT) void topk_rows_kernel(const TopkRowsArgs A) {
-  constexpr int KS = (int)sizeof(KT);
+__device__ __forceinline__ uint32_t wg_select_sort(const SelectArgs& a, uint32_t kk, uint32_t cap,
+                                                   bool select, U* sk, uint32_t* si, uint32_t* h) {
   constexpr int NW = NT / 64;
   constexpr int TILE = NT * kRowItems;
   constexpr int NB = 1 << kHistMaxBits;
@@ -5373,233 +5397,259 @@ __global__ __launch_bounds__(NT) void topk_rows_kernel(const TopkRowsArgs A) {
   constexpr uint32_t kSpare = (uint32_t)NB;
   static_assert(NB % NT == 0, "the bin walk gives every thread whole bins");
   static_assert(kRowItems * NW <= NT, "one thread per (slot, wave) count");
-  extern __shared__ __attribute__((aligned(16))) unsigned char topk_rows_lds[];
   __shared__ uint32_t scan_sh[NW + 1];
   __shared__ uint32_t wcnt[kRowItems * NW];  // per (slot, wave): sure | candidates << 16
   __shared__ unsigned long long bc[5];       // bucket, records below it, its size, OR, inverted AND
+  const int t = (int)threadIdx.x, wave = t >> 6;
+  const int kb = a.key_bits;
+  const uint64_t kmask = kb == 64 ? ~0ull : ((1ull << kb) - 1);
+  const uint32_t n = (uint32_t)a.n;
+  const Xform<U> xf = select_xform<U>(a);
+  U raw[kRowItems];
+  if constexpr (!STREAM) {
+    select_load<KT, U, false, NT, kRowItems>(a, 0, (int)n, raw);
+#pragma unroll
+    for (int k = 0; k < kRowItems; k++) raw[k] = xf(raw[k]);
+  }
+
+  // ---- which records: the prefix of the boundary bucket --------------------
+  uint64_t prefix = 0;        // the fixed top bits, in place
+  int fixed = 0, top = kb;    // the next digit ends below bit `top`
+  uint32_t k_rem = kk, cand = n;  // the rank wanted inside the prefix's bucket; its size
+  bool resolved = false;      // the bucket's keys are all equal
+  uint32_t passes = 0;
+  while (select && !resolved && cand != k_rem && (kk - k_rem) + cand > cap) {
+    const int bits = min(kHistMaxBits, top), shift = top - bits;
+    const bool all = fixed == 0;
+    const int psh = all ? 0 : kb - fixed;
+    const U pv = all ? (U)0 : (U)(prefix >> psh);
+    const uint32_t nb = 1u << bits, mask = nb - 1;
+    for (uint32_t i = t; i < nb; i += NT) h[i] = 0;
+    if (t < 5) bc[t] = 0;
+    __syncthreads();
+    U vor = 0, vnand = 0;
+    auto count = [&](U u, bool ok) {
+      ok = ok && (all || (U)(u >> psh) == pv);
+      vor |= ok ? u : (U)0;
+      vnand |= ok ? (U)~u : (U)0;
+      select_hist_add(h, ok ? ((uint32_t)(u >> shift) & mask) : kSpare, kSpare);
+    };
+    if constexpr (STREAM) {
+      for (uint32_t base = 0; base < n; base += TILE) {
+        const int cnt = (int)min((uint32_t)TILE, n - base);
+        select_load<KT, U, true, NT, kRowItems>(a, base, cnt, raw);
+        const bool full = cnt == TILE;  // (a partial tile is always read in element order)
+#pragma unroll
+        for (int k = 0; k < kRowItems; k++) count(xf(raw[k]), full || k * NT + t < cnt);
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < kRowItems; k++) count(raw[k], (uint32_t)(k * NT + t) < n);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      vor |= __shfl_xor(vor, o, 64);
+      vnand |= __shfl_xor(vnand, o, 64);
+    }
+    if (lane_id() == 0) {
+      atomicOr(&bc[3], (unsigned long long)vor);
+      atomicOr(&bc[4], (unsigned long long)vnand);
+    }
+    __syncthreads();
+    {  // the bucket that holds rank k_rem: a block scan over the threads' bin sums
+      uint32_t c[BPT], s = 0;
+#pragma unroll
+      for (int i = 0; i < BPT; i++) {
+        const uint32_t bin = (uint32_t)(t * BPT + i);
+        c[i] = bin < nb ? h[bin] : 0u;
+        s += c[i];
+      }
+      uint32_t tot;
+      uint32_t below = block_excl_scan<NT>(s, scan_sh, &tot);
+      if (below < k_rem && k_rem <= below + s) {
+#pragma unroll
+        for (int i = 0; i < BPT; i++) {
+          if (below + c[i] >= k_rem) {
+            bc[0] = (unsigned long long)(t * BPT + i);
+            bc[1] = below;
+            bc[2] = c[i];
+            break;
+          }
+          below += c[i];
+        }
+      }
+    }
+    __syncthreads();
+    const uint64_t b = bc[0], hor = bc[3], hnand = bc[4];
+    k_rem -= (uint32_t)bc[1];
+    cand = (uint32_t)bc[2];
+    __syncthreads();  // (bc and h are written again by the next pass)
+    passes++;
+    prefix |= b << shift;
+    fixed = kb - shift;
+    // where the bucket's parent still varies below this digit: the next
+    // digit starts at its highest varying bit, the bits between are shared
+    const uint64_t low = (1ull << shift) - 1;  // (shift <= 52)
+    const uint64_t vand = ~hnand & kmask;
+    const uint64_t var = (hor ^ vand) & low;
+    if (var == 0) {
+      resolved = true;
+      prefix |= vand & low;
+      fixed = kb;
+    } else {
+      const int hb = 63 - __builtin_clzll(var);
+      if (cand != k_rem && (kk - k_rem) + cand > cap) {
+        prefix |= vand & low & ~((2ull << hb) - 1);
+        fixed = kb - (hb + 1);
+        top = hb + 1;
+      }
+    }
+  }
+
+  // ---- the selected records into LDS, in input order -----------------------
+  // everything below the prefix, and the bucket itself (a bucket of equal
+  // keys: only its first k_rem records)
+  const bool all = fixed == 0;
+  const int psh = all ? 0 : kb - fixed;
+  const U pv = all ? (U)0 : (U)(prefix >> psh);
+  const uint32_t nsure = kk - k_rem;
+  const uint32_t climit = resolved ? k_rem : cand;
+  const uint32_t m = min(nsure + climit, cap);  // (never above cap: the stop rule)
+  uint32_t rs = 0, rc = 0;  // sure records / candidates before this tile
+  for (uint32_t base = 0; base < n; base += TILE) {
+    const int cnt = (int)min((uint32_t)TILE, n - base);
+    if constexpr (STREAM) {
+      select_load<KT, U, false, NT, kRowItems>(a, base, cnt, raw);
+#pragma unroll
+      for (int k = 0; k < kRowItems; k++) raw[k] = xf(raw[k]);
+    }
+    uint32_t cls = 0;  // 2 bits per slot: 1 sure, 2 candidate
+    uint32_t rk[kRowItems];
+#pragma unroll
+    for (int k = 0; k < kRowItems; k++) {
+      const bool ok = k * NT + t < cnt;
+      const U x = (U)(raw[k] >> psh);
+      const bool s = ok && !all && x < pv;
+      const bool c = ok && (all || x == pv);
+      const uint64_t bs = __ballot(s), bcand = __ballot(c);
+      rk[k] = popc_below(s ? bs : bcand);
+      cls |= (s ? 1u : c ? 2u : 0u) << (2 * k);
+      if (lane_id() == 0) wcnt[k * NW + wave] = (uint32_t)__popcll(bs) | ((uint32_t)__popcll(bcand) << 16);
+    }
+    __syncthreads();
+    uint32_t tot;
+    const uint32_t v = t < kRowItems * NW ? wcnt[t] : 0u;
+    const uint32_t pre = block_excl_scan<NT>(v, scan_sh, &tot);  // (a tile's counts stay below 2^16)
+    if (t < kRowItems * NW) wcnt[t] = pre;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kRowItems; k++) {
+      const uint32_t c = (cls >> (2 * k)) & 3u;
+      const uint32_t p = wcnt[k * NW + wave];
+      const uint32_t rank_c = rc + (p >> 16) + rk[k];
+      const uint32_t slot = c == 1 ? rs + (p & 0xffffu) + rk[k] : nsure + rank_c;
+      if ((c == 1 || (c == 2 && rank_c < climit)) && slot < m) {
+        sk[slot] = raw[k];
+        si[slot] = base + (uint32_t)(k * NT + t);
+      }
+    }
+    rs += tot & 0xffffu;
+    rc += tot >> 16;
+    __syncthreads();  // (wcnt is written again by the next tile)
+    if (rs >= nsure && rc >= climit) break;
+  }
+
+  // ---- sort by (key, position), padded to a power of two ---------------------
+  uint32_t p2 = 1;
+  while (p2 < m) p2 <<= 1;
+  for (uint32_t i = m + t; i < p2; i += NT) {
+    sk[i] = (U)~(U)0;
+    si[i] = 0xffffffffu;
+  }
+  __syncthreads();
+  rows_bitonic(sk, si, p2, (uint32_t)t, (uint32_t)NT, [] { __syncthreads(); });
+  return passes;
+}
+
+// One workgroup per row, grid-stride over the rows.
+template <typename KT, typename U, int NT, bool STREAM>
+__global__ __launch_bounds__(NT) void topk_rows_kernel(const TopkRowsArgs A) {
+  constexpr int KS = (int)sizeof(KT);
+  extern __shared__ __attribute__((aligned(16))) unsigned char topk_rows_lds[];
   U* const sk = (U*)topk_rows_lds;                 // [cap] transformed keys of the selected records
   uint32_t* const si = (uint32_t*)(sk + A.cap);    // [cap] their positions in the row
   uint32_t* const h = si + A.cap;                  // [NB] (select only)
-  const int t = (int)threadIdx.x, wave = t >> 6;
-  const int kb = A.key_bits;
-  const uint64_t kmask = kb == 64 ? ~0ull : ((1ull << kb) - 1);
-  const uint32_t n = (uint32_t)A.row_len, kk = (uint32_t)A.kk, cap = (uint32_t)A.cap;
+  const uint32_t t = threadIdx.x;
 
   for (int64_t row = blockIdx.x; row < A.rows; row += gridDim.x) {
     SelectArgs a;
     a.keys = A.col[0].in + row * A.row_stride * KS;
     a.stride = (uint32_t)KS;
-    a.n = n;
-    a.key_bits = kb;
+    a.n = A.row_len;
+    a.key_bits = A.key_bits;
     a.mpos = A.mpos;
     a.mneg = A.mneg;
-    const Xform<U> xf = select_xform<U>(a);
-    U raw[kRowItems];
-    if constexpr (!STREAM) {
-      select_load<KT, U, false, NT, kRowItems>(a, 0, (int)n, raw);
-#pragma unroll
-      for (int k = 0; k < kRowItems; k++) raw[k] = xf(raw[k]);
-    }
-
-    // ---- which records: the prefix of the boundary bucket --------------------
-    uint64_t prefix = 0;        // the fixed top bits, in place
-    int fixed = 0, top = kb;    // the next digit ends below bit `top`
-    uint32_t k_rem = kk, cand = n;  // the rank wanted inside the prefix's bucket; its size
-    bool resolved = false;      // the bucket's keys are all equal
-    uint32_t passes = 0;
-    while (A.select && !resolved && cand != k_rem && (kk - k_rem) + cand > cap) {
-      const int bits = min(kHistMaxBits, top), shift = top - bits;
-      const bool all = fixed == 0;
-      const int psh = all ? 0 : kb - fixed;
-      const U pv = all ? (U)0 : (U)(prefix >> psh);
-      const uint32_t nb = 1u << bits, mask = nb - 1;
-      for (uint32_t i = t; i < nb; i += NT) h[i] = 0;
-      if (t < 5) bc[t] = 0;
-      __syncthreads();
-      U vor = 0, vnand = 0;
-      auto count = [&](U u, bool ok) {
-        ok = ok && (all || (U)(u >> psh) == pv);
-        vor |= ok ? u : (U)0;
-        vnand |= ok ? (U)~u : (U)0;
-        select_hist_add(h, ok ? ((uint32_t)(u >> shift) & mask) : kSpare, kSpare);
-      };
-      if constexpr (STREAM) {
-        for (uint32_t base = 0; base < n; base += TILE) {
-          const int cnt = (int)min((uint32_t)TILE, n - base);
-          select_load<KT, U, true, NT, kRowItems>(a, base, cnt, raw);
-          const bool full = cnt == TILE;  // (a partial tile is always read in element order)
-#pragma unroll
-          for (int k = 0; k < kRowItems; k++) count(xf(raw[k]), full || k * NT + t < cnt);
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < kRowItems; k++) count(raw[k], (uint32_t)(k * NT + t) < n);
-      }
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) {
-        vor |= __shfl_xor(vor, o, 64);
-        vnand |= __shfl_xor(vnand, o, 64);
-      }
-      if (lane_id() == 0) {
-        atomicOr(&bc[3], (unsigned long long)vor);
-        atomicOr(&bc[4], (unsigned long long)vnand);
-      }
-      __syncthreads();
-      {  // the bucket that holds rank k_rem: a block scan over the threads' bin sums
-        uint32_t c[BPT], s = 0;
-#pragma unroll
-        for (int i = 0; i < BPT; i++) {
-          const uint32_t bin = (uint32_t)(t * BPT + i);
-          c[i] = bin < nb ? h[bin] : 0u;
-          s += c[i];
-        }
-        uint32_t tot;
-        uint32_t below = block_excl_scan<NT>(s, scan_sh, &tot);
-        if (below < k_rem && k_rem <= below + s) {
-#pragma unroll
-          for (int i = 0; i < BPT; i++) {
-            if (below + c[i] >= k_rem) {
-              bc[0] = (unsigned long long)(t * BPT + i);
-              bc[1] = below;
-              bc[2] = c[i];
-              break;
-            }
-            below += c[i];
-          }
-        }
-      }
-      __syncthreads();
-      const uint64_t b = bc[0], hor = bc[3], hnand = bc[4];
-      k_rem -= (uint32_t)bc[1];
-      cand = (uint32_t)bc[2];
-      __syncthreads();  // (bc and h are written again by the next pass)
-      passes++;
-      prefix |= b << shift;
-      fixed = kb - shift;
-      // where the bucket's parent still varies below this digit: the next
-      // digit starts at its highest varying bit, the bits between are shared
-      const uint64_t low = (1ull << shift) - 1;  // (shift <= 52)
-      const uint64_t vand = ~hnand & kmask;
-      const uint64_t var = (hor ^ vand) & low;
-      if (var == 0) {
-        resolved = true;
-        prefix |= vand & low;
-        fixed = kb;
-      } else {
-        const int hb = 63 - __builtin_clzll(var);
-        if (cand != k_rem && (kk - k_rem) + cand > cap) {
-          prefix |= vand & low & ~((2ull << hb) - 1);
-          fixed = kb - (hb + 1);
-          top = hb + 1;
-        }
-      }
-    }
-
-    // ---- the selected records into LDS, in input order -----------------------
-    // everything below the prefix, and the bucket itself (a bucket of equal
-    // keys: only its first k_rem records)
-    const bool all = fixed == 0;
-    const int psh = all ? 0 : kb - fixed;
-    const U pv = all ? (U)0 : (U)(prefix >> psh);
-    const uint32_t nsure = kk - k_rem;
-    const uint32_t climit = resolved ? k_rem : cand;
-    const uint32_t m = min(nsure + climit, cap);  // (never above cap: the stop rule)
-    uint32_t rs = 0, rc = 0;  // sure records / candidates before this tile
-    for (uint32_t base = 0; base < n; base += TILE) {
-      const int cnt = (int)min((uint32_t)TILE, n - base);
-      if constexpr (STREAM) {
-        select_load<KT, U, false, NT, kRowItems>(a, base, cnt, raw);
-#pragma unroll
-        for (int k = 0; k < kRowItems; k++) raw[k] = xf(raw[k]);
-      }
-      uint32_t cls = 0;  // 2 bits per slot: 1 sure, 2 candidate
-      uint32_t rk[kRowItems];
-#pragma unroll
-      for (int k = 0; k < kRowItems; k++) {
-        const bool ok = k * NT + t < cnt;
-        const U x = (U)(raw[k] >> psh);
-        const bool s = ok && !all && x < pv;
-        const bool c = ok && (all || x == pv);
-        const uint64_t bs = __ballot(s), bcand = __ballot(c);
-        rk[k] = popc_below(s ? bs : bcand);
-        cls |= (s ? 1u : c ? 2u : 0u) << (2 * k);
-        if (lane_id() == 0) wcnt[k * NW + wave] = (uint32_t)__popcll(bs) | ((uint32_t)__popcll(bcand) << 16);
-      }
-      __syncthreads();
-      uint32_t tot;
-      const uint32_t v = t < kRowItems * NW ? wcnt[t] : 0u;
-      const uint32_t pre = block_excl_scan<NT>(v, scan_sh, &tot);  // (a tile's counts stay below 2^16)
-      if (t < kRowItems * NW) wcnt[t] = pre;
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < kRowItems; k++) {
-        const uint32_t c = (cls >> (2 * k)) & 3u;
-        const uint32_t p = wcnt[k * NW + wave];
-        const uint32_t rank_c = rc + (p >> 16) + rk[k];
-        const uint32_t slot = c == 1 ? rs + (p & 0xffffu) + rk[k] : nsure + rank_c;
-        if ((c == 1 || (c == 2 && rank_c < climit)) && slot < m) {
-          sk[slot] = raw[k];
-          si[slot] = base + (uint32_t)(k * NT + t);
-        }
-      }
-      rs += tot & 0xffffu;
-      rc += tot >> 16;
-      __syncthreads();  // (wcnt is written again by the next tile)
-      if (rs >= nsure && rc >= climit) break;
-    }
-
-    // ---- sort by (key, position), padded to a power of two ---------------------
-    uint32_t p2 = 1;
-    while (p2 < m) p2 <<= 1;
-    for (uint32_t i = m + t; i < p2; i += NT) {
-      sk[i] = (U)~(U)0;
-      si[i] = 0xffffffffu;
-    }
-    __syncthreads();
-    rows_bitonic(sk, si, p2, (uint32_t)t, (uint32_t)NT, [] { __syncthreads(); });
+    const uint32_t passes = wg_select_sort<KT, U, NT, STREAM>(a, (uint32_t)A.kk, (uint32_t)A.cap,
+                                                              A.select != 0, sk, si, h);
 
     // ---- the first kk records, every column read by position -----------------
-    rows_write<KT>(A, row, si, (uint32_t)t, (uint32_t)NT);
+    write_by_position<KT>(A.col, A.ncols, A.idx_out, row * A.row_stride, row * A.kk,
+                          (uint32_t)A.row_len, (uint32_t)A.kk, si, t, (uint32_t)NT);
     if (t == 0 && passes > (uint32_t)gld<unsigned long long>(A.max_passes))
       atomicMax(A.max_passes, (unsigned long long)passes);
     __syncthreads();  // (the LDS slots are the next row's)
   }
 }
 
-size_t topk_rows_lds_bytes(int key_size, const TopkRowsArgs& a) {
-  const size_t u = key_size == 8 ? 8 : 4;
-  return (size_t)a.cap * (u + 4) + (a.select ? sizeof(uint32_t) << kHistMaxBits : 0);
+// The select's LDS slots: a power of two >= min(want, route_cap) records.
+static int32_t topk_select_cap(int64_t want, int64_t route_cap) {
+  int64_t cap = 2;
+  while (cap < std::min(want, route_cap)) cap <<= 1;
+  return (int32_t)cap;
+}
+
+// Dynamic LDS of a select workgroup: cap (transformed key, position) pairs,
+// and the histogram when it refines.
+static size_t topk_rows_lds_bytes(int key_size, int64_t cap, bool select) {
+  const size_t u = (key_size & 0xff) == 8 ? 8 : 4;
+  return (size_t)cap * (u + 4) + (select ? sizeof(uint32_t) << kHistMaxBits : 0);
+}
+
+// Launches kern with `lds` bytes of dynamic LDS, raising the kernel's limit
+// first when the request is above the 48 KB default.
+template <typename Args>
+static hipError_t launch_with_lds(void (*kern)(Args), unsigned grid, unsigned nt, size_t lds,
+                                  hipStream_t st, const Args& a) {
+  if (lds > 48 * 1024) {
+    const hipError_t err = hipFuncSetAttribute(
+        (const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (err != hipSuccess) return err;
+  }
+  kern<<<grid, nt, lds, st>>>(a);
+  return hipGetLastError();
 }
 
 hipError_t launch_topk_rows(int key_size, TopkRowsArgs& a, bool stream, hipStream_t st) {
   // the stop rule's capacity: rows up to max(2 kk, kTopkRowsMinCap) records
   // are sorted whole; longer ones are refined down to that many slots
-  int64_t fit = std::max<int64_t>(2 * a.kk, kTopkRowsMinCap);
-  const int64_t route_cap = stream ? kTopkRowsStreamCap : kLocalCap;
+  const int64_t fit = std::max<int64_t>(2 * a.kk, kTopkRowsMinCap);
   a.select = a.row_len > fit;
-  int64_t want = std::min(a.select ? fit : a.row_len, route_cap), cap = 2;
-  while (cap < want) cap <<= 1;
-  a.cap = (int32_t)cap;
-  hipError_t err = hipSuccess;
+  a.cap = topk_select_cap(a.select ? fit : a.row_len, stream ? kTopkRowsStreamCap : kLocalCap);
+  const size_t lds = topk_rows_lds_bytes(key_size, a.cap, a.select);
   constexpr int64_t kWaveRows = kRowsWaveThreads / 64;
   if (!stream && a.row_len <= kRowsWaveMax && (a.rows + kWaveRows - 1) / kWaveRows <= 0x7fffffff) {
     const unsigned grid = (unsigned)((a.rows + kWaveRows - 1) / kWaveRows);
-    const size_t lds = kWaveRows * (topk_rows_lds_bytes(key_size, a));  // (select == 0 here)
-#define CALL(KT, U, CZ) topk_rows_wave_kernel<KT, U><<<grid, kRowsWaveThreads, lds, st>>>(a)
+    // (select == 0 here: kWaveRows slabs of cap pairs)
+#define CALL(KT, U, CZ) \
+  topk_rows_wave_kernel<KT, U><<<grid, kRowsWaveThreads, kWaveRows * lds, st>>>(a)
     SRS_KEY_DISPATCH(key_size, CALL)
 #undef CALL
     return hipGetLastError();
   }
-  const size_t lds = topk_rows_lds_bytes(key_size, a);
   const unsigned grid = (unsigned)std::min<int64_t>(a.rows, 0x7fffffff);
-#define ROWS_GO(KT, U, NT, STREAM)                                                       \
-  do {                                                                                   \
-    auto kern = topk_rows_kernel<KT, U, NT, STREAM>;                                     \
-    if (lds > 48 * 1024)                                                                 \
-      err = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)lds);                                               \
-    if (err == hipSuccess) kern<<<grid, NT, lds, st>>>(a);                               \
-  } while (0)
+  hipError_t err = hipSuccess;
+#define ROWS_GO(KT, U, NT, STREAM) \
+  err = launch_with_lds(topk_rows_kernel<KT, U, NT, STREAM>, grid, NT, lds, st, a)
 #define CALL(KT, U, CZ)                                                 \
   do {                                                                  \
     if (stream) ROWS_GO(KT, U, 1024, true);                             \
@@ -5611,7 +5661,7 @@ hipError_t launch_topk_rows(int key_size, TopkRowsArgs& a, bool stream, hipStrea
   SRS_KEY_DISPATCH(key_size, CALL)
 #undef CALL
 #undef ROWS_GO
-  return err != hipSuccess ? err : hipGetLastError();
+  return err;
 }
 
 // ---------------------------------------------------------------------------
@@ -5720,28 +5770,22 @@ __device__ __forceinline__ bool ragged_bounds(const int64_t* __restrict__ offset
   return a >= 0 && a <= b && b <= num;
 }
 
-// rows_write for a segment of n records at `at` of the input and of the
-// output columns: record j of the result is input record si[j] of the segment.
-template <typename KT>
-__device__ __forceinline__ void ragged_write(const RaggedArgs& A, int64_t at, uint32_t n,
-                                             const uint32_t* si, uint32_t lane) {
-  constexpr int KS = (int)sizeof(KT);
-  for (uint32_t j = lane; j < n; j += 64) {
-    const uint32_t e = si[j];
-    if (e >= n) continue;  // (a padding slot: never inside the first n)
-    stw<KS>(A.col[0].out + (at + j) * KS, (uint64_t)gld<KT>(A.col[0].in + (at + e) * KS));
-    if (A.idx_out) gst<int64_t>(A.idx_out + at + j, (int64_t)e);
+// The segment record e lies in, kept from the previous record while e stays
+// inside it (len < 0: none yet), else found by a search of the offsets (the
+// last s with offsets[s] <= e). The bounds found are tested before anything
+// is touched: len = -1 unless they are valid.
+__device__ __forceinline__ void ragged_segment_of(const int64_t* __restrict__ offsets,
+                                                  int64_t nseg, int64_t num, int64_t e,
+                                                  int64_t* seg, int64_t* at, int64_t* len) {
+  if (*len >= 0 && e >= *at && e - *at < *len) return;
+  int64_t lo = 0, hi = nseg;
+  while (hi - lo > 1) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if (offsets[mid] <= e) lo = mid;
+    else hi = mid;
   }
-  for (int c = 1; c < A.ncols; c++) {
-    const TopkRowsCol& C = A.col[c];
-    with_width(C.width, [&](auto W_) {
-      constexpr int W = decltype(W_)::value;
-      for (uint32_t j = lane; j < n; j += 64) {
-        const uint32_t e = si[j];
-        if (e < n) stw<W>(C.out + (at + j) * W, ldw<W>(C.in + (at + e) * W));
-      }
-    });
-  }
+  *seg = lo;
+  if (!ragged_bounds(offsets, lo, num, at, len)) *len = -1;
 }
 
 // One WAVE per segment, four segments to a workgroup, no workgroup barrier:
@@ -5768,20 +5812,9 @@ __global__ __launch_bounds__(kRaggedShortThreads) void ragged_short_kernel(const
   while (p2 < n) p2 <<= 1;
   U* const sk = ragged_sk + wave * kRowsWaveMax;
   uint32_t* const si = ragged_si + wave * kRowsWaveMax;
-  SelectArgs a;
-  a.key_bits = A.key_bits;
-  a.mpos = A.mpos;
-  a.mneg = A.mneg;
-  const Xform<U> xf = select_xform<U>(a);
-  const char* keys = A.col[0].in + at * KS;
-  for (uint32_t e = lane; e < p2; e += 64) {
-    const bool ok = e < n;
-    sk[e] = ok ? xf((U)gld<KT>(keys + (int64_t)e * KS)) : (U)~(U)0;
-    si[e] = ok ? e : 0xffffffffu;
-  }
-  wave_lds_sync();
-  rows_bitonic(sk, si, p2, lane, 64u, [] { wave_lds_sync(); });
-  ragged_write<KT>(A, at, n, si, lane);
+  wave_sort_segment<KT, U>(A.col[0].in + at * KS, n, p2, sk, si,
+                           select_xform<U>(A.key_bits, A.mpos, A.mneg), lane);
+  write_by_position<KT>(A.col, A.ncols, A.idx_out, at, at, n, n, si, lane, 64u);
 }
 
 // One thread per segment: the listed segments (valid, longer than short_max)
@@ -5815,28 +5848,18 @@ __global__ __launch_bounds__(kRaggedSegsThreads) void ragged_segs_kernel(
 // their in-segment positions: element-parallel over [0, num), so one long
 // segment is spread over as many workgroups as it has strips. Thread t of a
 // block takes records t, t + 256, ... of the block's 1024 consecutive
-// positions; it finds its first record's segment by a search of the offsets
-// (the last s with offsets[s] <= e) and keeps it while the next records stay
-// inside. The bounds found are tested before anything is touched: a record is
+// positions, and finds their segments with ragged_segment_of: a record is
 // copied only when it lies in a valid segment longer than short_max.
 __global__ __launch_bounds__(kRaggedPrepThreads) void ragged_prepare_kernel(const RaggedArgs A) {
   const int64_t e0 = (int64_t)blockIdx.x * (kRaggedPrepThreads * kRaggedPrepItems) + threadIdx.x;
   int64_t pos[kRaggedPrepItems];  // in-segment position, or -1: not copied
-  int64_t at = 0, len = -1;       // the segment of the previous record (len < 0: none)
+  int64_t at = 0, len = -1, seg = 0;  // the segment of the previous record (len < 0: none)
 #pragma unroll
   for (int k = 0; k < kRaggedPrepItems; k++) {
     const int64_t e = e0 + k * kRaggedPrepThreads;
     pos[k] = -1;
     if (e >= A.num) continue;
-    if (len < 0 || e < at || e - at >= len) {
-      int64_t lo = 0, hi = A.nseg;
-      while (hi - lo > 1) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (A.offsets[mid] <= e) lo = mid;
-        else hi = mid;
-      }
-      if (!ragged_bounds(A.offsets, lo, A.num, &at, &len)) len = -1;
-    }
+    ragged_segment_of(A.offsets, A.nseg, A.num, e, &seg, &at, &len);
     if (len > A.short_max && e >= at && e - at < len) pos[k] = e - at;
   }
   for (int c = 0; c < A.ncols; c++) {
@@ -5901,32 +5924,6 @@ hipError_t launch_ragged_prepare(const RaggedArgs& a, hipStream_t st) {
 constexpr int kTopkRaggedThreads = 256;      // classify, the wave kernel, the head copy
 constexpr int kTopkRaggedItems = 4;          // the head copy's records per thread
 constexpr int kTopkRaggedLongThreads = 1024;
-
-// rows_write for the first c records of a segment of n at `at` of the input
-// columns, to slots out0 .. out0 + c of the outputs: result j is input
-// record si[j] of the segment.
-template <typename KT>
-__device__ __forceinline__ void topk_ragged_write(const TopkRaggedArgs& A, int64_t at,
-                                                  int64_t out0, uint32_t n, uint32_t c,
-                                                  const uint32_t* si, uint32_t t, uint32_t nt) {
-  constexpr int KS = (int)sizeof(KT);
-  for (uint32_t j = t; j < c; j += nt) {
-    const uint32_t e = si[j];
-    if (e >= n) continue;  // (a padding slot: never inside the first c)
-    stw<KS>(A.col[0].out + (out0 + j) * KS, (uint64_t)gld<KT>(A.col[0].in + (at + e) * KS));
-    if (A.idx_out) gst<int64_t>(A.idx_out + out0 + j, (int64_t)e);
-  }
-  for (int q = 1; q < A.ncols; q++) {
-    const TopkRowsCol& C = A.col[q];
-    with_width(C.width, [&](auto W_) {
-      constexpr int W = decltype(W_)::value;
-      for (uint32_t j = t; j < c; j += nt) {
-        const uint32_t e = si[j];
-        if (e < n) stw<W>(C.out + (out0 + j) * W, ldw<W>(C.in + (at + e) * W));
-      }
-    });
-  }
-}
 
 // One thread per segment: counts_out, the bad / empty / short / long counts
 // (one atomic per wave and counter), and the list of the long segments, whose
@@ -5996,50 +5993,27 @@ __global__ __launch_bounds__(kTopkRaggedThreads) void topk_ragged_short_kernel(
   while (p2 < n) p2 <<= 1;
   U* const sk = tkr_sk + wave * kRowsWaveMax;
   uint32_t* const si = tkr_si + wave * kRowsWaveMax;
-  SelectArgs a;
-  a.key_bits = A.key_bits;
-  a.mpos = A.mpos;
-  a.mneg = A.mneg;
-  const Xform<U> xf = select_xform<U>(a);
-  const char* keys = A.col[0].in + at * KS;
-  for (uint32_t e = lane; e < p2; e += 64) {
-    const bool ok = e < n;
-    sk[e] = ok ? xf((U)gld<KT>(keys + (int64_t)e * KS)) : (U)~(U)0;
-    si[e] = ok ? e : 0xffffffffu;
-  }
-  wave_lds_sync();
-  rows_bitonic(sk, si, p2, lane, 64u, [] { wave_lds_sync(); });
-  topk_ragged_write<KT>(A, at, s * A.k, n, (uint32_t)min((int64_t)n, A.k), si, lane, 64u);
+  wave_sort_segment<KT, U>(A.col[0].in + at * KS, n, p2, sk, si,
+                           select_xform<U>(A.key_bits, A.mpos, A.mneg), lane);
+  write_by_position<KT>(A.col, A.ncols, A.idx_out, at, s * A.k, n,
+                        (uint32_t)min((int64_t)n, A.k), si, lane, 64u);
 }
 
 // topk_rows_kernel's streamed form with the segment's own length and start:
 // one workgroup per listed segment, grid-stride over the list. The list's
 // length and the segment's bounds are read from memory no kernel of the call
 // writes after the classify pass, the same way in every thread, so the trip
-// counts and every condition around a barrier are uniform over the workgroup.
-// A.cap slots (>= 2 k): a segment of at most A.cap records is sorted whole,
-// with no histogram pass.
+// counts and what wg_select_sort is called with are uniform over the
+// workgroup. A.cap slots (>= 2 k): a segment of at most A.cap records is
+// sorted whole, with no histogram pass.
 template <typename KT, typename U, int NT>
 __global__ __launch_bounds__(NT) void topk_ragged_long_kernel(const TopkRaggedArgs A) {
   constexpr int KS = (int)sizeof(KT);
-  constexpr int NW = NT / 64;
-  constexpr int TILE = NT * kRowItems;
-  constexpr int NB = 1 << kHistMaxBits;
-  constexpr int BPT = NB / NT > 0 ? NB / NT : 1;  // histogram bins a thread sums
-  constexpr uint32_t kSpare = (uint32_t)NB;
-  static_assert(NB % NT == 0, "the bin walk gives every thread whole bins");
-  static_assert(kRowItems * NW <= NT, "one thread per (slot, wave) count");
   extern __shared__ __attribute__((aligned(16))) unsigned char topk_ragged_lds[];
-  __shared__ uint32_t scan_sh[NW + 1];
-  __shared__ uint32_t wcnt[kRowItems * NW];  // per (slot, wave): sure | candidates << 16
-  __shared__ unsigned long long bc[5];       // bucket, records below it, its size, OR, inverted AND
   U* const sk = (U*)topk_ragged_lds;               // [cap] transformed keys of the selected records
   uint32_t* const si = (uint32_t*)(sk + A.cap);    // [cap] their positions in the segment
   uint32_t* const h = si + A.cap;                  // [NB]
-  const int t = (int)threadIdx.x, wave = t >> 6;
-  const int kb = A.key_bits;
-  const uint64_t kmask = kb == 64 ? ~0ull : ((1ull << kb) - 1);
-  const uint32_t cap = (uint32_t)A.cap;
+  const uint32_t t = threadIdx.x;
   const unsigned long long nlist = min(gld<unsigned long long>(&A.ctr->n_long), A.list_cap);
 
   for (unsigned long long li = blockIdx.x; li < nlist; li += gridDim.x) {
@@ -6053,164 +6027,14 @@ __global__ __launch_bounds__(NT) void topk_ragged_long_kernel(const TopkRaggedAr
     a.keys = A.col[0].in + at * KS;
     a.stride = (uint32_t)KS;
     a.n = n;
-    a.key_bits = kb;
+    a.key_bits = A.key_bits;
     a.mpos = A.mpos;
     a.mneg = A.mneg;
-    const Xform<U> xf = select_xform<U>(a);
-    U raw[kRowItems];
-
-    // ---- which records: the prefix of the boundary bucket --------------------
-    uint64_t prefix = 0;        // the fixed top bits, in place
-    int fixed = 0, top = kb;    // the next digit ends below bit `top`
-    uint32_t k_rem = kk, cand = n;  // the rank wanted inside the prefix's bucket; its size
-    bool resolved = false;      // the bucket's keys are all equal
-    uint32_t passes = 0;
-    while (!resolved && cand != k_rem && (kk - k_rem) + cand > cap) {
-      const int bits = min(kHistMaxBits, top), shift = top - bits;
-      const bool all = fixed == 0;
-      const int psh = all ? 0 : kb - fixed;
-      const U pv = all ? (U)0 : (U)(prefix >> psh);
-      const uint32_t nb = 1u << bits, mask = nb - 1;
-      for (uint32_t i = t; i < nb; i += NT) h[i] = 0;
-      if (t < 5) bc[t] = 0;
-      __syncthreads();
-      U vor = 0, vnand = 0;
-      for (uint32_t base = 0; base < n; base += TILE) {
-        const int cnt = (int)min((uint32_t)TILE, n - base);
-        select_load<KT, U, true, NT, kRowItems>(a, base, cnt, raw);
-        const bool full = cnt == TILE;  // (a partial tile is always read in element order)
-#pragma unroll
-        for (int q = 0; q < kRowItems; q++) {
-          const U u = xf(raw[q]);
-          const bool ok = (full || q * NT + t < cnt) && (all || (U)(u >> psh) == pv);
-          vor |= ok ? u : (U)0;
-          vnand |= ok ? (U)~u : (U)0;
-          select_hist_add(h, ok ? ((uint32_t)(u >> shift) & mask) : kSpare, kSpare);
-        }
-      }
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) {
-        vor |= __shfl_xor(vor, o, 64);
-        vnand |= __shfl_xor(vnand, o, 64);
-      }
-      if (lane_id() == 0) {
-        atomicOr(&bc[3], (unsigned long long)vor);
-        atomicOr(&bc[4], (unsigned long long)vnand);
-      }
-      __syncthreads();
-      {  // the bucket that holds rank k_rem: a block scan over the threads' bin sums
-        uint32_t c[BPT], s = 0;
-#pragma unroll
-        for (int i = 0; i < BPT; i++) {
-          const uint32_t bin = (uint32_t)(t * BPT + i);
-          c[i] = bin < nb ? h[bin] : 0u;
-          s += c[i];
-        }
-        uint32_t tot;
-        uint32_t below = block_excl_scan<NT>(s, scan_sh, &tot);
-        if (below < k_rem && k_rem <= below + s) {
-#pragma unroll
-          for (int i = 0; i < BPT; i++) {
-            if (below + c[i] >= k_rem) {
-              bc[0] = (unsigned long long)(t * BPT + i);
-              bc[1] = below;
-              bc[2] = c[i];
-              break;
-            }
-            below += c[i];
-          }
-        }
-      }
-      __syncthreads();
-      const uint64_t b = bc[0], hor = bc[3], hnand = bc[4];
-      k_rem -= (uint32_t)bc[1];
-      cand = (uint32_t)bc[2];
-      __syncthreads();  // (bc and h are written again by the next pass)
-      passes++;
-      prefix |= b << shift;
-      fixed = kb - shift;
-      // where the bucket's parent still varies below this digit: the next
-      // digit starts at its highest varying bit, the bits between are shared
-      const uint64_t low = (1ull << shift) - 1;  // (shift <= 52)
-      const uint64_t vand = ~hnand & kmask;
-      const uint64_t var = (hor ^ vand) & low;
-      if (var == 0) {
-        resolved = true;
-        prefix |= vand & low;
-        fixed = kb;
-      } else {
-        const int hb = 63 - __builtin_clzll(var);
-        if (cand != k_rem && (kk - k_rem) + cand > cap) {
-          prefix |= vand & low & ~((2ull << hb) - 1);
-          fixed = kb - (hb + 1);
-          top = hb + 1;
-        }
-      }
-    }
-
-    // ---- the selected records into LDS, in input order -----------------------
-    // everything below the prefix, and the bucket itself (a bucket of equal
-    // keys: only its first k_rem records)
-    const bool all = fixed == 0;
-    const int psh = all ? 0 : kb - fixed;
-    const U pv = all ? (U)0 : (U)(prefix >> psh);
-    const uint32_t nsure = kk - k_rem;
-    const uint32_t climit = resolved ? k_rem : cand;
-    const uint32_t m = min(nsure + climit, cap);  // (never above cap: the stop rule)
-    uint32_t rs = 0, rc = 0;  // sure records / candidates before this tile
-    for (uint32_t base = 0; base < n; base += TILE) {
-      const int cnt = (int)min((uint32_t)TILE, n - base);
-      select_load<KT, U, false, NT, kRowItems>(a, base, cnt, raw);
-#pragma unroll
-      for (int q = 0; q < kRowItems; q++) raw[q] = xf(raw[q]);
-      uint32_t cls = 0;  // 2 bits per slot: 1 sure, 2 candidate
-      uint32_t rk[kRowItems];
-#pragma unroll
-      for (int q = 0; q < kRowItems; q++) {
-        const bool ok = q * NT + t < cnt;
-        const U x = (U)(raw[q] >> psh);
-        const bool s = ok && !all && x < pv;
-        const bool c = ok && (all || x == pv);
-        const uint64_t bs = __ballot(s), bcand = __ballot(c);
-        rk[q] = popc_below(s ? bs : bcand);
-        cls |= (s ? 1u : c ? 2u : 0u) << (2 * q);
-        if (lane_id() == 0) wcnt[q * NW + wave] = (uint32_t)__popcll(bs) | ((uint32_t)__popcll(bcand) << 16);
-      }
-      __syncthreads();
-      uint32_t tot;
-      const uint32_t v = t < kRowItems * NW ? wcnt[t] : 0u;
-      const uint32_t pre = block_excl_scan<NT>(v, scan_sh, &tot);  // (a tile's counts stay below 2^16)
-      if (t < kRowItems * NW) wcnt[t] = pre;
-      __syncthreads();
-#pragma unroll
-      for (int q = 0; q < kRowItems; q++) {
-        const uint32_t c = (cls >> (2 * q)) & 3u;
-        const uint32_t p = wcnt[q * NW + wave];
-        const uint32_t rank_c = rc + (p >> 16) + rk[q];
-        const uint32_t slot = c == 1 ? rs + (p & 0xffffu) + rk[q] : nsure + rank_c;
-        if ((c == 1 || (c == 2 && rank_c < climit)) && slot < m) {
-          sk[slot] = raw[q];
-          si[slot] = base + (uint32_t)(q * NT + t);
-        }
-      }
-      rs += tot & 0xffffu;
-      rc += tot >> 16;
-      __syncthreads();  // (wcnt is written again by the next tile)
-      if (rs >= nsure && rc >= climit) break;
-    }
-
-    // ---- sort by (key, position), padded to a power of two ---------------------
-    uint32_t p2 = 1;
-    while (p2 < m) p2 <<= 1;
-    for (uint32_t i = m + t; i < p2; i += NT) {
-      sk[i] = (U)~(U)0;
-      si[i] = 0xffffffffu;
-    }
-    __syncthreads();
-    rows_bitonic(sk, si, p2, (uint32_t)t, (uint32_t)NT, [] { __syncthreads(); });
+    const uint32_t passes =
+        wg_select_sort<KT, U, NT, true>(a, kk, (uint32_t)A.cap, true, sk, si, h);
 
     // ---- the first kk records, every column read by position -----------------
-    topk_ragged_write<KT>(A, at, seg * A.k, n, kk, si, (uint32_t)t, (uint32_t)NT);
+    write_by_position<KT>(A.col, A.ncols, A.idx_out, at, seg * A.k, n, kk, si, t, (uint32_t)NT);
     if (t == 0 && passes > (uint32_t)gld<unsigned long long>(&A.ctr->max_passes))
       atomicMax(&A.ctr->max_passes, (unsigned long long)passes);
     __syncthreads();  // (the LDS slots are the next segment's)
@@ -6218,9 +6042,9 @@ __global__ __launch_bounds__(NT) void topk_ragged_long_kernel(const TopkRaggedAr
 }
 
 // The sort route's head copy, element-parallel over [0, num) as
-// ragged_prepare_kernel is: a thread finds its record's segment by a search
-// of the offsets, tests the bounds found before anything is touched, and
-// copies the record when it lies among the first k of a valid segment.
+// ragged_prepare_kernel is: a thread finds its record's segment with
+// ragged_segment_of and copies the record when it lies among the first k of
+// a valid segment.
 __global__ __launch_bounds__(kTopkRaggedThreads) void topk_ragged_heads_kernel(
     const TopkRaggedArgs A) {
   const int64_t e0 = (int64_t)blockIdx.x * (kTopkRaggedThreads * kTopkRaggedItems) + threadIdx.x;
@@ -6231,16 +6055,7 @@ __global__ __launch_bounds__(kTopkRaggedThreads) void topk_ragged_heads_kernel(
     const int64_t e = e0 + q * kTopkRaggedThreads;
     dst[q] = -1;
     if (e >= A.num) continue;
-    if (len < 0 || e < at || e - at >= len) {
-      int64_t lo = 0, hi = A.nseg;
-      while (hi - lo > 1) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (A.offsets[mid] <= e) lo = mid;
-        else hi = mid;
-      }
-      seg = lo;
-      if (!ragged_bounds(A.offsets, lo, A.num, &at, &len)) len = -1;
-    }
+    ragged_segment_of(A.offsets, A.nseg, A.num, e, &seg, &at, &len);
     if (len > 0 && e >= at && e - at < len && e - at < A.k) dst[q] = seg * A.k + (e - at);
   }
   for (int c = 0; c < A.ncols; c++) {
@@ -6288,13 +6103,8 @@ hipError_t launch_topk_ragged_long(int key_size, TopkRaggedArgs& a, hipStream_t 
     return hipErrorInvalidValue;
   // the stop rule's capacity, from k alone: segments of up to cap records are
   // sorted whole; longer ones are refined down to that many slots
-  const int64_t want = std::min<int64_t>(std::max<int64_t>(2 * a.k, kTopkRowsMinCap),
-                                         kTopkRowsStreamCap);
-  int64_t cap = 2;
-  while (cap < want) cap <<= 1;
-  a.cap = (int32_t)cap;
-  const size_t lds = (size_t)cap * ((key_size & 0xff) == 8 ? 12 : 8) +
-                     (sizeof(uint32_t) << kHistMaxBits);
+  a.cap = topk_select_cap(std::max<int64_t>(2 * a.k, kTopkRowsMinCap), kTopkRowsStreamCap);
+  const size_t lds = topk_rows_lds_bytes(key_size, a.cap, true);
   int dev = 0, cus = 0;
   hipError_t err = hipGetDevice(&dev);
   if (err == hipSuccess) err = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
@@ -6302,17 +6112,12 @@ hipError_t launch_topk_ragged_long(int key_size, TopkRaggedArgs& a, hipStream_t 
   // (a workgroup per listed segment, at most four per CU: the rest of the
   // list is taken grid-stride; its length is only known on the device)
   const unsigned grid = (unsigned)std::min<unsigned long long>(a.list_cap, 4ull * (unsigned)std::max(cus, 1));
-#define CALL(KT, U, CZ)                                                                     \
-  do {                                                                                      \
-    auto kern = topk_ragged_long_kernel<KT, U, kTopkRaggedLongThreads>;                     \
-    if (lds > 48 * 1024)                                                                    \
-      err = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)lds);                                                  \
-    if (err == hipSuccess) kern<<<grid, kTopkRaggedLongThreads, lds, st>>>(a);              \
-  } while (0)
+#define CALL(KT, U, CZ)                                                                  \
+  err = launch_with_lds(topk_ragged_long_kernel<KT, U, kTopkRaggedLongThreads>, grid,    \
+                        kTopkRaggedLongThreads, lds, st, a)
   SRS_KEY_DISPATCH(key_size, CALL)
 #undef CALL
-  return err != hipSuccess ? err : hipGetLastError();
+  return err;
 }
 
 hipError_t launch_topk_ragged_heads(const TopkRaggedArgs& a, hipStream_t st) {

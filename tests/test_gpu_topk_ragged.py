@@ -161,10 +161,7 @@ def test_routes_agree_and_equal_the_sorts_head(torch, name, indices):
                 assert np.array_equal(g[a:b], want), f"k={k} column {q} segment {i}"
 
 
-@pytest.mark.parametrize("indices", [False, True])
-def test_uniform_offsets_equal_topk_rows(torch, indices):
-    rows, n, k = 300, 700, 50
-    kind, cols = _column_set("u64_u64", 0, rows * n, rows)
+def _uniform_equals_topk_rows(torch, kind, cols, rows, n, k, indices):
     offs = np.arange(rows + 1, dtype=np.int64) * n
     got = tl.run(torch, srs_amd, kind, True, cols, offs, k, indices, what="uniform")
     assert srs_amd.debug_last_topk_ragged()[:3] == (tl.KERNELS, 0, rows)
@@ -177,6 +174,31 @@ def test_uniform_offsets_equal_topk_rows(torch, indices):
             assert np.array_equal(a, tl.to_bytes(r)), f"column {q} differs from topk_rows_device"
         else:
             assert np.array_equal(a, r.cpu().numpy().reshape(-1)), "indices differ"
+
+
+@pytest.mark.parametrize("indices", [False, True])
+def test_uniform_offsets_equal_topk_rows(torch, indices):
+    """the long kernel against the rows call's resident instance (300 x 700),
+    then against its stream instance, whose select the long kernel runs: rows
+    of 9001 records (above kLocalCap = 8192: one full tile and a partial one),
+    k = 16 (256 slots), keys equal above bit 20, so the first digit resolves
+    nothing and a second pass, from the highest varying bit, is needed"""
+    rows, n, k = 300, 700, 50
+    kind, cols = _column_set("u64_u64", 0, rows * n, rows)
+    _uniform_equals_topk_rows(torch, kind, cols, rows, n, k, indices)
+
+    rows, n, k = 3, 9001, 16
+    rng = np.random.default_rng(9001)
+    keys = (np.uint64(0xABCDE) << np.uint64(20)) | rng.integers(0, 1 << 20, rows * n,
+                                                                 dtype=np.uint64)
+    top = keys.reshape(rows, n) >> np.uint64(52)
+    assert (top == top[:, :1]).all() and n > 256 and n > 8192  # the first pass keeps every record
+    _uniform_equals_topk_rows(torch, U64, [keys, np.arange(rows * n, dtype=np.uint64)], rows, n, k,
+                              indices)
+    info_rows, info_ragged = srs_amd.debug_last_topk_rows(), srs_amd.debug_last_topk_ragged()
+    assert info_rows[0] == srs_amd.TOPK_ROWS_STREAM, info_rows
+    assert info_rows[2] == info_ragged[3], (info_rows, info_ragged)
+    assert info_rows[2] >= 2, info_rows
 
 
 # ---------------------------------------------------------------------------
