@@ -18,6 +18,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from srs_shard_fuzzlib import _chunk_bound, _chunk_hists, _top
 from srs_testlib import KIND_UINT, key_size, transformed_keys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,31 +34,6 @@ def _shard():
     sys.path.insert(0, os.path.join(REPO, "simd-radix-sort_amd", "python"))
     from srs_amd import shard
     return shard
-
-
-def _top(kind, keys, bits):
-    return (transformed_keys(kind, True, keys) >> np.uint64(8 * key_size(kind) - bits)).astype(
-        np.int64)
-
-
-def _chunk_bound(n, c, chunks):
-    """The library's chunk bounds (srs_shard.hip chunk_bound): the first
-    chunk weighs 1, every other 4."""
-    if c <= 0:
-        return 0
-    if c >= chunks:
-        return n
-    return n * (4 * c - 3) // (4 * chunks - 3)
-
-
-def _chunk_hists(kind, keys, chunks, bits):
-    n = len(keys)
-    out = np.zeros((chunks, 1 << bits), np.uint64)
-    top = _top(kind, keys, bits)
-    for c in range(chunks):
-        a, b = _chunk_bound(n, c, chunks), _chunk_bound(n, c + 1, chunks)
-        out[c] = np.bincount(top[a:b], minlength=1 << bits)
-    return out
 
 
 def _make_keys(kind, dist_kind, n, rng):
