@@ -462,6 +462,38 @@ void search_sorted(void* stream, const SortIndex num, const K* const sorted_keys
                 "device::search_sorted");
 }
 
+// merge: two sorted record sets (num_a records in keys_a, num_b in keys_b,
+// both in the sort's key order; Up = false: both sorted descending) merged
+// stably into keys_out and every payload's third array, num_a + num_b records
+// (srs_merge_soa_device): the stable sort of A followed by B, A's records
+// first among equal keys. Every payload is (A's array, B's array, the output
+// array). source_out (device, num_a + num_b int64; may be null) receives
+// every output record's position in that concatenation. Out of place; the
+// call does not wait for the device. The second form has no source_out.
+template <bool Up = true, typename K, typename... Ps>
+void merge(void* stream, const SortIndex num_a, const K* const keys_a, const SortIndex num_b,
+           const K* const keys_b, K* const keys_out, int64_t* const source_out,
+           std::tuple<const Ps*, const Ps*, Ps*>... payloads) {
+  static_assert(detail::key_kind<K>() >= 0, "unsupported key type");
+  static_assert((detail::valid_payload<Ps> && ...), "payload sizes must be 1, 2, 4 or 8");
+  static_assert(sizeof...(Ps) <= SRS_MAX_PAYLOADS, "too many payload arrays");
+  const void* pays_a[sizeof...(Ps) + 1] = {(const void*)std::get<0>(payloads)..., nullptr};
+  const void* pays_b[sizeof...(Ps) + 1] = {(const void*)std::get<1>(payloads)..., nullptr};
+  void* pays_out[sizeof...(Ps) + 1] = {(void*)std::get<2>(payloads)..., nullptr};
+  uint32_t sizes[sizeof...(Ps) + 1] = {(uint32_t)sizeof(Ps)..., 0};
+  detail::check(srs_merge_soa_device((int64_t)num_a, (int64_t)num_b, detail::key_kind<K>(),
+                                     Up ? 1 : 0, (const void*)keys_a, (const void*)keys_b,
+                                     (int32_t)sizeof...(Ps), pays_a, pays_b, sizes,
+                                     (void*)keys_out, pays_out, source_out, stream),
+                "device::merge");
+}
+template <bool Up = true, typename K, typename... Ps>
+void merge(void* stream, const SortIndex num_a, const K* const keys_a, const SortIndex num_b,
+           const K* const keys_b, K* const keys_out,
+           std::tuple<const Ps*, const Ps*, Ps*>... payloads) {
+  merge<Up>(stream, num_a, keys_a, num_b, keys_b, keys_out, (int64_t*)nullptr, payloads...);
+}
+
 }  // namespace device
 }  // namespace radix_sort
 }  // namespace simd_sort

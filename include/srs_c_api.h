@@ -448,6 +448,44 @@ int srs_search_sorted_device(int64_t num, int key_kind, int up, const void* sort
                              int64_t* upper_out, int64_t* num_bad_dev, int32_t flags,
                              void* stream);
 
+/* Merge: two sorted record sets combined into one, stably, in one call. Let
+ * T be the key transform of (key_kind, up), exactly search-sorted's (floats
+ * in the total order, so -0.0 sorts before +0.0; up == 0 means that BOTH
+ * inputs are sorted descending; uint64 keys have their own kind; NaN keys are
+ * outside the contract). keys_a[0, num_a) and keys_b[0, num_b) each have T
+ * non-decreasing: anything a total-order call of this library wrote. Payload
+ * column c of A and of B has the same width payload_sizes[c] (1, 2, 4 or 8);
+ * 0 .. SRS_MAX_PAYLOADS columns, every key kind. The inputs are never
+ * written.
+ * Output: num_a + num_b records in keys_out and in every payloads_out[c],
+ * equal to the stable sort by T of A followed by B: among equal keys all of
+ * A's records come first, in A's order, then B's in B's order. source_out
+ * (may be NULL, num_a + num_b int64) receives every output record's position
+ * in that concatenation, i for A[i] and num_a + j for B[j]: the argsort of
+ * the concatenation, with which a caller gathers columns it did not pass.
+ * Out of place only: every output is checked against every input column and
+ * against every other output, and an overlap is SRS_ERR_INVALID_ARG.
+ * An input that is not sorted gives an unspecified result, but nothing
+ * outside the given columns is read or written and every source_out value
+ * lies in [0, num_a + num_b).
+ * num_a + num_b <= 0 is a no-op. One empty side is legal, its pointers may
+ * then be NULL, and the call is an ordered copy of the other side.
+ * Checked before any device access: key_kind, the payload sizes,
+ * num_payloads out of range, negative counts, (num_a + num_b) * 16
+ * overflowing, NULL columns of a side that is not empty, NULL outputs,
+ * misaligned pointers (keys and payloads to their element size, source_out
+ * to 8 bytes), and the overlaps above.
+ * Host waits: none. Nothing is read back; the call queues three launches on
+ * `stream` (the column descriptor, the split of every tile boundary, one
+ * workgroup per SRS_MERGE_TILE output records) and returns.
+ * The only workspace is 8 bytes per tile. */
+#define SRS_MERGE_TILE 4096 /* output records per workgroup, for tests of the kernel's edges */
+int srs_merge_soa_device(int64_t num_a, int64_t num_b, int key_kind, int up,
+                         const void* keys_a, const void* keys_b, int32_t num_payloads,
+                         const void* const* payloads_a, const void* const* payloads_b,
+                         const uint32_t* payload_sizes, void* keys_out,
+                         void* const* payloads_out, int64_t* source_out, void* stream);
+
 /* ---- multi-GPU shard primitives (top-radix-bits partition) --
  * A node-wide sort of one array spread over N GPUs: every rank histograms
  * its keys' top bits (srs_key_histogram_device), the histograms are summed
@@ -791,6 +829,13 @@ int srs_debug_set_search_route(int route);
  * = host read-backs during the call (0 on route 0; -1 on route 1: the sort's,
  * not counted), info[3] = 1 if the queries were sorted by the call. */
 int srs_debug_last_search(int64_t* info);
+
+/* What the last merge on the current device did (host state only: no
+ * synchronization): info[0] = launches queued (the descriptor, the split, the
+ * tiles: 3), info[1] = host read-backs (0), info[2] = tiles, info[3] = bytes
+ * of the workspace buffers the call uses (the split array and the column
+ * descriptor, as allocated). */
+int srs_debug_last_merge(int64_t* info);
 
 #ifdef __cplusplus
 }

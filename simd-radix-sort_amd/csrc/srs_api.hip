@@ -605,7 +605,7 @@ Workspace::~Workspace() {
                     &gsum, &gofs, &scan_tmp, &totals, &ctr, &prun, &ptile, &btot, &bnt, &btile,
                     &nt_over, &gtile, &gorder, &mid, &midbar, &sel, &selhist, &selcnt, &seldesc,
                     &rowspass, &sortrowspass, &tkrctr, &tkrlist, &tkrcols, &uniqcols,
-                    &uniqcnt, &searchcols};
+                    &uniqcnt, &searchcols, &mergesplit};
   for (DevBuf* b : bufs) free_buf(*b);
   for (auto& t : small_taken) free_buf(t.second);
   if (h_sel) (void)hipHostFree(h_sel);

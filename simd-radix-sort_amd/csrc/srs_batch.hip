@@ -1099,6 +1099,159 @@ int search_device(const SearchCall& C, hipStream_t st) {
   return SRS_OK;
 }
 
+// ---------------------------------------------------------------------------
+// merge: the split of A at every tile boundary, then one
+// workgroup per tile of the output; the columns' three views travel in the
+// gather's descriptor (A: BUF_IN, B: BUF_TMP, the output: BUF_OUT)
+// ---------------------------------------------------------------------------
+static_assert(kMergeTile == SRS_MERGE_TILE, "srs_c_api.h states the merge kernel's tile");
+
+struct MergeCall {
+  int64_t num_a, num_b;
+  int kind, up;
+  int ncols;  // the key column and the payload columns
+  const void* a[SRS_MAX_COLS];
+  const void* b[SRS_MAX_COLS];
+  void* out[SRS_MAX_COLS];
+  uint32_t widths[SRS_MAX_COLS];
+  int64_t* source;
+};
+
+// The raw arguments of srs_merge_soa_device, checked, into C: everything is
+// checked here, before the first device access. Messages name the argument
+// (and the payload column) at fault.
+int merge_validate(MergeCall& C, int64_t num_a, int64_t num_b, int key_kind, int up,
+                   const void* keys_a, const void* keys_b, int32_t num_payloads,
+                   const void* const* payloads_a, const void* const* payloads_b,
+                   const uint32_t* payload_sizes, void* keys_out, void* const* payloads_out,
+                   int64_t* source_out) {
+  memset(&C, 0, sizeof C);
+  if (key_size_of(key_kind) == 0) return fail(SRS_ERR_INVALID_ARG, "invalid key_kind");
+  if (num_payloads < 0 || num_payloads > SRS_MAX_PAYLOADS)
+    return fail(SRS_ERR_INVALID_ARG, "num_payloads out of range");
+  if (num_payloads > 0 && !payload_sizes)
+    return fail(SRS_ERR_INVALID_ARG, "payload_sizes is NULL");
+  C.widths[0] = (uint32_t)key_size_of(key_kind);
+  for (int i = 0; i < num_payloads; i++) {
+    const uint32_t w = payload_sizes[i];
+    if (w != 1 && w != 2 && w != 4 && w != 8)
+      return fail(SRS_ERR_UNSUPPORTED, "payload_sizes[" + std::to_string(i) +
+                                           "]: payload sizes must be 1, 2, 4 or 8 bytes");
+    C.widths[1 + i] = w;
+  }
+  if (num_a < 0) return fail(SRS_ERR_INVALID_ARG, "num_a is negative");
+  if (num_b < 0) return fail(SRS_ERR_INVALID_ARG, "num_b is negative");
+  int64_t n = 0;
+  if (__builtin_add_overflow(num_a, num_b, &n) || n > (INT64_MAX >> 4))
+    return fail(SRS_ERR_INVALID_ARG, "(num_a + num_b) * 16 overflows");
+  C.num_a = num_a;
+  C.num_b = num_b;
+  C.kind = key_kind;
+  C.up = up ? 1 : 0;
+  C.ncols = 1 + num_payloads;
+  C.source = source_out;
+  if (n == 0) return SRS_OK;  // (a no-op looks at none of the arrays)
+  if (num_payloads > 0 && num_a > 0 && !payloads_a)
+    return fail(SRS_ERR_INVALID_ARG, "payloads_a is NULL");
+  if (num_payloads > 0 && num_b > 0 && !payloads_b)
+    return fail(SRS_ERR_INVALID_ARG, "payloads_b is NULL");
+  if (num_payloads > 0 && !payloads_out) return fail(SRS_ERR_INVALID_ARG, "payloads_out is NULL");
+  C.a[0] = num_a > 0 ? keys_a : nullptr;
+  C.b[0] = num_b > 0 ? keys_b : nullptr;
+  C.out[0] = keys_out;
+  for (int i = 0; i < num_payloads; i++) {
+    C.a[1 + i] = num_a > 0 ? payloads_a[i] : nullptr;
+    C.b[1 + i] = num_b > 0 ? payloads_b[i] : nullptr;
+    C.out[1 + i] = payloads_out[i];
+  }
+  // column c's name on one side: keys_a, payloads_b[3], ...
+  auto name = [](int c, const char* side) {
+    return c == 0 ? std::string("keys_") + side
+                  : std::string("payloads_") + side + "[" + std::to_string(c - 1) + "]";
+  };
+  for (int c = 0; c < C.ncols; c++) {
+    if (num_a > 0 && !C.a[c]) return fail(SRS_ERR_INVALID_ARG, name(c, "a") + " is NULL");
+    if (num_b > 0 && !C.b[c]) return fail(SRS_ERR_INVALID_ARG, name(c, "b") + " is NULL");
+    if (!C.out[c]) return fail(SRS_ERR_INVALID_ARG, name(c, "out") + " is NULL");
+  }
+  for (int c = 0; c < C.ncols; c++) {
+    const uintptr_t w = C.widths[c];
+    const char* bad = (uintptr_t)C.a[c] % w != 0     ? "a"
+                      : (uintptr_t)C.b[c] % w != 0   ? "b"
+                      : (uintptr_t)C.out[c] % w != 0 ? "out"
+                                                     : nullptr;
+    if (bad)
+      return fail(SRS_ERR_INVALID_ARG,
+                  name(c, bad) + " must be aligned to its element size (" + std::to_string(w) +
+                      " bytes)");
+  }
+  if ((uintptr_t)C.source % 8 != 0) return fail(SRS_ERR_INVALID_ARG, "source_out must be 8-byte aligned");
+  UniqueOut ins[2 * SRS_MAX_COLS], outs[SRS_MAX_COLS + 1];
+  int ni = 0, no = 0;
+  for (int c = 0; c < C.ncols; c++) {
+    ins[ni++] = {C.a[c], (size_t)C.num_a * C.widths[c]};
+    ins[ni++] = {C.b[c], (size_t)C.num_b * C.widths[c]};
+    outs[no++] = {C.out[c], (size_t)n * C.widths[c]};
+  }
+  if (C.source) outs[no++] = {C.source, (size_t)n * 8};
+  auto over = [](const UniqueOut& p, const UniqueOut& q) {
+    const uintptr_t x = (uintptr_t)p.p, y = (uintptr_t)q.p;
+    return p.bytes && q.bytes && x < y + q.bytes && y < x + p.bytes;
+  };
+  for (int o = 0; o < no; o++)
+    for (int i = 0; i < ni; i++)
+      if (over(outs[o], ins[i]))
+        return fail(SRS_ERR_INVALID_ARG, "merge outputs must not overlap the inputs");
+  for (int o = 0; o < no; o++)
+    for (int q = o + 1; q < no; q++)
+      if (over(outs[o], outs[q]))
+        return fail(SRS_ERR_INVALID_ARG, "merge outputs must not overlap each other");
+  return SRS_OK;
+}
+
+int merge_device(const MergeCall& C, hipStream_t st) {
+  const int ks = key_size_of(C.kind);
+  const int64_t n = C.num_a + C.num_b;
+  const int64_t ntiles = (n + kMergeTile - 1) / kMergeTile;
+  if (ntiles > 0x7fffffff) return fail(SRS_ERR_UNSUPPORTED, "num_a + num_b: more than 2^31 - 1 tiles");
+  WsScope ws;
+  SRS_TRY(ws.begin(st));  // (the split buffer and the descriptor are the workspace's)
+  Workspace* W = ws.W;
+  int64_t* info = W->merge_info;
+  info[0] = info[1] = 0;
+  info[2] = ntiles;
+  SRS_TRY(ensure(W->mergesplit, (size_t)(ntiles + 1) * sizeof(int64_t)));
+  SRS_TRY(ensure(W->seldesc, sizeof(SortDesc)));
+  info[3] = (int64_t)(W->mergesplit.bytes + W->seldesc.bytes);
+
+  SortDesc d = init_desc(C.kind, C.up);
+  for (int c = 0; c < C.ncols; c++) {
+    const uint32_t w = C.widths[c];
+    d.cols[c] = Col{{(char*)C.a[c], (char*)C.out[c], (char*)C.b[c], nullptr}, w, {w, w, w, w}};
+  }
+  set_gather_desc(W, d, C.ncols, st);
+  MergeArgs a;
+  memset(&a, 0, sizeof a);
+  a.num_a = C.num_a;
+  a.num_b = C.num_b;
+  a.desc = (const SortDesc*)W->seldesc.p;
+  a.split = (int64_t*)W->mergesplit.p;
+  a.source = C.source;
+  a.key_bits = d.key_bits;
+  a.mpos = d.mpos;
+  a.mneg = d.mneg;
+  {
+    TimedScope ts("merge_split", (double)(ntiles + 1), st);
+    HIP_TRY(launch_merge_split(ks, a, st));
+  }
+  {
+    TimedScope ts("merge_tile", (double)n, st);
+    HIP_TRY(launch_merge_tile(ks, a, st));
+  }
+  info[0] = 3;  // the descriptor, the split, the tiles
+  return SRS_OK;
+}
+
 }  // namespace
 }  // namespace srs
 
@@ -1282,6 +1435,27 @@ int srs_debug_last_search(int64_t* info) {
   WsLock lk;
   SRS_TRY(acquire_ws(&W, &lk));
   for (int i = 0; i < 4; i++) info[i] = W->search_info[i];
+  return SRS_OK;
+}
+
+int srs_merge_soa_device(int64_t num_a, int64_t num_b, int key_kind, int up, const void* keys_a,
+                         const void* keys_b, int32_t num_payloads,
+                         const void* const* payloads_a, const void* const* payloads_b,
+                         const uint32_t* payload_sizes, void* keys_out, void* const* payloads_out,
+                         int64_t* source_out, void* stream) {
+  MergeCall C;
+  SRS_TRY(merge_validate(C, num_a, num_b, key_kind, up, keys_a, keys_b, num_payloads, payloads_a,
+                         payloads_b, payload_sizes, keys_out, payloads_out, source_out));
+  if (num_a + num_b <= 0) return SRS_OK;
+  return merge_device(C, (hipStream_t)stream);
+}
+
+int srs_debug_last_merge(int64_t* info) {
+  if (!info) return fail(SRS_ERR_INVALID_ARG, "info is NULL");
+  Workspace* W = nullptr;
+  WsLock lk;
+  SRS_TRY(acquire_ws(&W, &lk));
+  for (int i = 0; i < 4; i++) info[i] = W->merge_info[i];
   return SRS_OK;
 }
 

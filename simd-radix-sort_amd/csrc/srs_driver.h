@@ -109,6 +109,10 @@ struct Workspace {
   // what the last call did
   DevBuf searchcols;
   int64_t search_info[4] = {0, 0, 0, 0};
+  // merge: the tile boundaries' split of A (int64 per boundary); what the last
+  // call did
+  DevBuf mergesplit;
+  int64_t merge_info[4] = {0, 0, 0, 0};
   hipStream_t side = nullptr;  // medium sorts: the large local class's stream
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   ListCounters* h_ctr = nullptr;

@@ -360,4 +360,32 @@ constexpr int kSearchSamples = 2048;
 constexpr int kSearchFit = kSearchSamples - 1;
 hipError_t launch_search(int key_size, const SearchArgs& a, hipStream_t st);
 
+// ---- merge ---------------------------------------------------
+// The stable merge of two dense record sets A (num_a) and B (num_b) whose
+// transformed keys do not decrease, A's records first among equal keys. The
+// columns travel in *desc: column c of A is cols[c]'s BUF_IN view, of B its
+// BUF_TMP view, of the output its BUF_OUT view (dense: stride == width;
+// cols[0] the key column). split: ntiles + 1 int64, ntiles = ceil((num_a +
+// num_b) / kMergeTile): split[t] = the records of A among the first min(t *
+// kMergeTile, n) of the output. source (or null) receives every output
+// record's position in A followed by B. No record outside [0, num_a) of A,
+// [0, num_b) of B and [0, num_a + num_b) of the outputs is accessed whatever
+// the keys and the split array hold.
+struct MergeArgs {
+  int64_t num_a, num_b;
+  const SortDesc* desc;
+  int64_t* split;
+  int64_t* source;      // or null
+  int32_t key_bits;
+  uint64_t mpos, mneg;  // SortDesc's key transform
+};
+constexpr int kMergeThreads = 256;
+constexpr int kMergeItems = 16;
+constexpr int kMergeTile = kMergeThreads * kMergeItems;  // output records per workgroup
+// One thread per tile boundary: the merge path's diagonal bisected.
+hipError_t launch_merge_split(int key_size, const MergeArgs& a, hipStream_t st);
+// One workgroup per tile: both key ranges staged in LDS, ranked against each
+// other, every column written in output order.
+hipError_t launch_merge_tile(int key_size, const MergeArgs& a, hipStream_t st);
+
 }  // namespace srs

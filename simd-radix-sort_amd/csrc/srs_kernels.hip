@@ -6390,4 +6390,185 @@ hipError_t launch_search(int key_size, const SearchArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// merge (srs_merge_soa_device)
+//
+// Merge path in two launches in stream order. merge_split_kernel bisects the
+// diagonal of every tile boundary: split[t] is how many of the first min(t *
+// kMergeTile, n) output records come from A. merge_tile_kernel then owns
+// output records [t * kMergeTile, (t + 1) * kMergeTile): it stages the
+// transformed keys of its A range and its B range in LDS, ranks every staged
+// key in the other range (an A key goes behind the B keys strictly below it,
+// a B key behind the A keys at or below it: A first among equal keys), turns
+// the ranks into the source slot of every output slot, and writes every
+// column in output order, read through that source slot from the tile's two
+// contiguous ranges. No workgroup waits for another and there is no atomic.
+// Both kernels bound every index themselves (see MergeArgs): an input that
+// is not sorted gives an unspecified order, never an access outside.
+// ---------------------------------------------------------------------------
+static_assert(kMergeItems * kMergeThreads == kMergeTile && kMergeTile <= 65536 &&
+                  (kMergeTile & (kMergeTile - 1)) == 0,
+              "merge block shape: u16 source slots, a power-of-two rank walk");
+
+template <typename U>
+__device__ __forceinline__ Xform<U> merge_xform(const MergeArgs& a) {
+  Xform<U> xf;
+  xf.mpos = (U)a.mpos;
+  xf.cdiff = (U)(a.mpos ^ a.mneg);
+  xf.negzero = 0;
+  xf.sbit = a.key_bits - 1;
+  xf.canon = false;
+  return xf;
+}
+
+template <typename KT, typename U>
+__global__ __launch_bounds__(kMergeThreads) void merge_split_kernel(const MergeArgs a,
+                                                                    int64_t ntiles) {
+  constexpr int KS = (int)sizeof(KT);
+  const int64_t t = (int64_t)blockIdx.x * kMergeThreads + threadIdx.x;
+  if (t > ntiles) return;
+  const int64_t n = a.num_a + a.num_b;
+  const int64_t d = min(t * kMergeTile, n);
+  const char* ka = a.desc->cols[0].base[BUF_IN];
+  const char* kb = a.desc->cols[0].base[BUF_TMP];
+  const Xform<U> xf = merge_xform<U>(a);
+  // lo <= hi stay inside [max(0, d - num_b), min(d, num_a)]: mid < num_a and
+  // 0 <= d - 1 - mid < num_b whatever the keys hold
+  int64_t lo = max((int64_t)0, d - a.num_b), hi = min(d, a.num_a);
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    const U x = xf((U)gld<KT>(ka + mid * KS));
+    const U y = xf((U)gld<KT>(kb + (d - 1 - mid) * KS));
+    if (x <= y) lo = mid + 1;
+    else hi = mid;
+  }
+  gst<int64_t>(a.split + t, lo);
+}
+
+template <typename KT, typename U>
+__global__ __launch_bounds__(kMergeThreads) void merge_tile_kernel(const MergeArgs a) {
+  constexpr int KS = (int)sizeof(KT);
+  __shared__ U sk[kMergeTile];           // T(A range), then T(B range)
+  __shared__ uint16_t ssrc[kMergeTile];  // output slot -> staged slot
+  const int t = (int)threadIdx.x;
+  const int64_t n = a.num_a + a.num_b;
+  const int64_t d0 = (int64_t)blockIdx.x * kMergeTile;
+  const int64_t d1 = min(d0 + kMergeTile, n);
+  const int cnt = (int)(d1 - d0);
+  // the tile's ranges, valid whatever split holds: a0 and a1 on their own
+  // diagonals, then a1 within [a0, a0 + cnt], so that na + nb == cnt
+  const int64_t a0 = min(max(gld<int64_t>(a.split + blockIdx.x), max((int64_t)0, d0 - a.num_b)),
+                         min(d0, a.num_a));
+  int64_t a1 = min(max(gld<int64_t>(a.split + blockIdx.x + 1), max((int64_t)0, d1 - a.num_b)),
+                   min(d1, a.num_a));
+  a1 = min(max(a1, a0), a0 + cnt);
+  const int64_t b0 = d0 - a0;
+  const int na = (int)(a1 - a0), nb = cnt - na;
+  const SortDesc* __restrict__ desc = a.desc;
+  const Xform<U> xf = merge_xform<U>(a);
+
+  // ---- both key ranges, transformed, into LDS ----------------------------------
+  U x[kMergeItems];
+  {
+    const char* ka = desc->cols[0].base[BUF_IN] + a0 * KS;
+    const char* kb = desc->cols[0].base[BUF_TMP] + b0 * KS;
+#pragma unroll
+    for (int k = 0; k < kMergeItems; k++) {
+      const int e = k * kMergeThreads + t;
+      x[k] = 0;
+      if (e < cnt) {
+        x[k] = xf((U)gld<KT>(e < na ? ka + (int64_t)e * KS : kb + (int64_t)(e - na) * KS));
+        sk[e] = x[k];
+        ssrc[e] = 0;  // (a slot no rank reaches, unsorted inputs only, reads staged slot 0)
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- ranks: the staged keys of the other range below (B: at or below) -------
+  uint32_t c[kMergeItems];
+#pragma unroll
+  for (int k = 0; k < kMergeItems; k++) c[k] = 0;
+  uint32_t w0 = 1;
+  while (2 * w0 <= (uint32_t)max(na, nb)) w0 *= 2;
+  for (uint32_t w = w0; w; w >>= 1) {
+#pragma unroll
+    for (int k = 0; k < kMergeItems; k++) {
+      const int e = k * kMergeThreads + t;
+      const bool is_a = e < na;
+      const uint32_t p = c[k] + w;
+      const bool in = e < cnt && p <= (uint32_t)(is_a ? nb : na);
+      const U s = sk[in ? (is_a ? na : 0) + p - 1 : 0];
+      if (in && (s < x[k] || (!is_a && s == x[k]))) c[k] = p;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kMergeItems; k++) {
+    const int e = k * kMergeThreads + t;
+    const uint32_t dst = (uint32_t)(e < na ? e : e - na) + c[k];
+    if (e < cnt && dst < (uint32_t)cnt) ssrc[dst] = (uint16_t)e;
+  }
+  __syncthreads();
+
+  // ---- every column in output order, read through the source slot -------------
+  // s[k]: the staged slot of output slot k * kMergeThreads + t (< na: record a0
+  // + s of A, else record b0 + s - na of B); -1: no such output slot. Columns
+  // move in two halves of the items: fewer registers, one more workgroup per CU.
+  int s[kMergeItems];
+#pragma unroll
+  for (int k = 0; k < kMergeItems; k++) {
+    const int d = k * kMergeThreads + t;
+    s[k] = d < cnt ? (int)ssrc[d] : -1;
+  }
+  constexpr int H = kMergeItems / 2;
+  const int ncols = desc->ncols;
+  for (int col = 0; col < ncols; col++) {
+    const Col& C = desc->cols[col];
+    const int64_t w = C.width;
+    const char* pa = C.base[BUF_IN] + a0 * w;
+    const char* pb = C.base[BUF_TMP] + (b0 - na) * w;
+    char* po = C.base[BUF_OUT] + d0 * w;
+    with_width(C.width, [&](auto W_) {
+      constexpr int W = decltype(W_)::value;
+#pragma unroll
+      for (int h = 0; h < kMergeItems; h += H) {
+        uint64_t v[H];
+#pragma unroll
+        for (int k = 0; k < H; k++)
+          v[k] = s[h + k] >= 0 ? ldw<W>((s[h + k] < na ? pa : pb) + (int64_t)s[h + k] * W) : 0;
+#pragma unroll
+        for (int k = 0; k < H; k++)
+          if (s[h + k] >= 0) stw<W>(po + (int64_t)((h + k) * kMergeThreads + t) * W, v[k]);
+      }
+    });
+  }
+  if (a.source) {
+    const int64_t sb = a.num_a + b0 - na;
+#pragma unroll
+    for (int k = 0; k < kMergeItems; k++)
+      if (s[k] >= 0)
+        gst<int64_t>(a.source + d0 + k * kMergeThreads + t, s[k] < na ? a0 + s[k] : sb + s[k]);
+  }
+}
+
+hipError_t launch_merge_split(int key_size, const MergeArgs& a, hipStream_t st) {
+  const int64_t ntiles = (a.num_a + a.num_b + kMergeTile - 1) / kMergeTile;
+  const int64_t grid = (ntiles + 1 + kMergeThreads - 1) / kMergeThreads;
+  if (ntiles <= 0 || grid > 0x7fffffff) return hipErrorInvalidValue;
+#define CALL(KT, U, CZ) \
+  merge_split_kernel<KT, U><<<(unsigned)grid, kMergeThreads, 0, st>>>(a, ntiles)
+  SRS_KEY_DISPATCH(key_size, CALL)
+#undef CALL
+  return hipGetLastError();
+}
+
+hipError_t launch_merge_tile(int key_size, const MergeArgs& a, hipStream_t st) {
+  const int64_t ntiles = (a.num_a + a.num_b + kMergeTile - 1) / kMergeTile;
+  if (ntiles <= 0 || ntiles > 0x7fffffff) return hipErrorInvalidValue;
+#define CALL(KT, U, CZ) merge_tile_kernel<KT, U><<<(unsigned)ntiles, kMergeThreads, 0, st>>>(a)
+  SRS_KEY_DISPATCH(key_size, CALL)
+#undef CALL
+  return hipGetLastError();
+}
+
 }  // namespace srs

@@ -103,6 +103,9 @@ def lib() -> ctypes.CDLL:
                                            vp, vp, vp, vp, i32, vp]
     L.srs_debug_set_search_route.argtypes = [ctypes.c_int]
     L.srs_debug_last_search.argtypes = [ctypes.POINTER(i64)]
+    L.srs_merge_soa_device.argtypes = [i64, i64, ctypes.c_int, ctypes.c_int, vp, vp, i32, vp, vp,
+                                       vp, vp, vp, vp, vp]
+    L.srs_debug_last_merge.argtypes = [ctypes.POINTER(i64)]
     L.srs_fill_synthetic_device.argtypes = [i64, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
                                             vp, i32, vp, vp, vp]
     L.srs_key_histogram_device.argtypes = [i64, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp,
@@ -703,6 +706,69 @@ def debug_last_search():
     searchsorted_device on the current device."""
     c = (ctypes.c_int64 * 4)()
     _check(lib().srs_debug_last_search(c))
+    return tuple(int(x) for x in c)
+
+
+MERGE_TILE = 4096  # srs_c_api.h: SRS_MERGE_TILE, output records per workgroup
+
+
+def merge_device(a, b, *, up: bool = True, key_kind: int | None = None, indices: bool = False,
+                 out=None, stream=None):
+    """Two sorted record sets merged stably in one call (srs_merge_soa_device).
+    `a` = (a_keys, *a_payloads) and `b` = (b_keys, *b_payloads) are 1-D
+    contiguous device columns with the same dtypes, column by column, on the
+    same GPU (TypeError / ValueError otherwise), each sorted in the library's
+    key order: what sort_device, the row-wise and ragged calls, unique_device
+    or an earlier merge wrote (floats in the total order; up=False: both
+    sorted descending; key_kind for uint64 keys held as int64). Returns
+    (keys, *payloads[, source]) of len(a) + len(b) records: the stable sort of
+    a followed by b, a's records first among equal keys. `out` = (keys_out,
+    *payloads_out) of at least that many elements each, or new tensors; with
+    indices=True an int64 tensor follows that holds every output record's
+    position in the concatenation (i for a[i], len(a) + j for b[j]). The
+    inputs are not written and must not overlap the outputs. The call does not
+    wait on the host."""
+    import torch
+    a, b = tuple(a), tuple(b)
+    if not a or len(a) != len(b):
+        raise ValueError("a and b must hold a key column and the same number of payload columns")
+    for t in a + b:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("a and b must hold tensors")
+    _check_columns(a[0], a, "a's columns")
+    _check_columns(b[0], b, "b's columns")
+    for x, y in zip(a, b):
+        if x.dtype != y.dtype:
+            raise TypeError(f"a and b must have the same column dtypes ({x.dtype} and {y.dtype})")
+    dev = a[0].device
+    if b[0].device != dev:
+        raise ValueError(f"a and b must be on the same GPU ({dev} and {b[0].device})")
+    kind = _torch_kind(a[0]) if key_kind is None else int(key_kind)
+    na, nb = a[0].numel(), b[0].numel()
+    n = na + nb
+    out = _out_columns(out, a, (n,),
+                       "out tensors must be 1-D contiguous, on the inputs' GPU, of at least "
+                       "len(a) + len(b) elements and of their input's element size")
+    src = torch.empty(n, dtype=torch.int64, device=dev) if indices else None
+    np_ = len(a) - 1
+    if n > 0:  # (an empty tensor has no address to pass)
+        with _on_device(a[0]):
+            _check(lib().srs_merge_soa_device(
+                na, nb, kind, int(bool(up)), a[0].data_ptr() if na else None,
+                b[0].data_ptr() if nb else None, np_,
+                _ptr_array([p.data_ptr() for p in a[1:]]) if np_ and na else None,
+                _ptr_array([p.data_ptr() for p in b[1:]]) if np_ and nb else None,
+                _size_array([p.element_size() for p in a[1:]]) if np_ else None,
+                out[0].data_ptr(), _ptr_array([o.data_ptr() for o in out[1:]]) if np_ else None,
+                None if src is None else src.data_ptr(), _stream_ptr(stream, dev)))
+    return out + ((src,) if indices else ())
+
+
+def debug_last_merge():
+    """(launches queued, host read-backs (0), tiles, bytes of the workspace
+    buffers used) of the last merge_device on the current device."""
+    c = (ctypes.c_int64 * 4)()
+    _check(lib().srs_debug_last_merge(c))
     return tuple(int(x) for x in c)
 
 
