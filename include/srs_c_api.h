@@ -683,6 +683,43 @@ int srs_kernel_stats(const char* name, int64_t* launches, double* total_ms,
  * tests lower it so that the path runs at small sizes. */
 int srs_debug_set_super_scan(int64_t min_groups);
 
+/* Test hook, process-wide and read on every call, like
+ * srs_debug_set_super_scan: the size rules that pick a sort's first level
+ * (DESIGN.md §2), so that the plain, balanced, stripe and gathered levels run
+ * at small sizes. It affects every entry point that ends in the sort driver
+ * (the device and host sorts, and the top-k, row-wise, ragged, unique, search
+ * and shard calls where they sort). Tests restore the defaults in a `finally`
+ * or a fixture. A value <= 0 restores that field's default; with every field
+ * at its default each decision of the driver is what it is without the hook.
+ *   general_min_n  sorts of at least this many records (and above the
+ *                  single-workgroup capacity) skip both one-launch starts and
+ *                  start with a plain level over one segment (default: off)
+ *   balanced_min_n the fewest records for which the key sample is taken
+ *                  (default 2^24)
+ *   stripe_min_n   the fewest records for the stripe first level (default
+ *                  2^25)
+ *   stripe_pairs   the stripe length in tile pairs of 8192 records, 1 .. 244
+ *                  (default: 3904 << b1 records, itself 61, 122 or 244 pairs
+ *                  for the digit widths 7, 8, 9 the planner produces); the
+ *                  rule n >= 2 stripes stays. A stripe level runs only after
+ *                  a plain start.
+ *   first_bits     the plain stripe level's digit width b1, 1 .. 9 (default:
+ *                  chosen from n, 7 .. 9 at the sizes the planner takes
+ *                  stripes at)
+ * Returns SRS_ERR_INVALID_ARG for stripe_pairs > 244 or first_bits > 9. */
+int srs_debug_set_first_level(int64_t general_min_n, int64_t balanced_min_n,
+                              int64_t stripe_min_n, int64_t stripe_pairs, int first_bits);
+
+/* What the last sort above the single-workgroup capacity did on the current
+ * device: out[0] = its start (0 plain, 1 the mid-size launch, 2 the mid-level
+ * launch; -1: no such sort has run), out[1] = the first level's kind (0 a
+ * plain digit, 1 the 16-bit digit table, 3 the split table, 2 a range
+ * level), out[2] = 1 when the stripe level and the gathered level ran,
+ * out[3] = the stripe count K, out[4] = the stripe level's digit width b1,
+ * out[5] = the gathered level's tile count (out[3..5] are 0 without
+ * stripes). */
+int srs_debug_last_first_level(int64_t* out);
+
 /* Global levels run in this process so far (every device, every entry point
  * that takes the general level driver): counts[0] = all of them, counts[1] =
  * those scattered by the tile-pair kernel, counts[2] = of those, the ones

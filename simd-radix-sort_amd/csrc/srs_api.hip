@@ -172,6 +172,18 @@ SRS_KNOB(const char*, table_knob, knob_str("SRS_TABLE"))
 // Read on every call (tests lower it to reach the kernel at small sizes).
 SRS_KNOB(int64_t, direct_min_segs, knob_int("SRS_DIRECT_MIN_SEGS", 8192))
 
+// The first level's size rules as a test sets them (srs_debug_set_first_level;
+// no environment knob): 0 in a field is its default. Read on every call.
+struct FirstLevelHook {
+  std::atomic<int64_t> general_min_n{0}, balanced_min_n{0}, stripe_min_n{0}, stripe_pairs{0};
+  std::atomic<int> first_bits{0};
+};
+FirstLevelHook g_first;
+int64_t hook_or(const std::atomic<int64_t>& v, int64_t dflt) {
+  const int64_t x = v.load(std::memory_order_relaxed);
+  return x > 0 ? x : dflt;
+}
+
 // ---------------------------------------------------------------------------
 // kernel timing (optional; HIP events around every launch on its stream)
 // ---------------------------------------------------------------------------
@@ -721,7 +733,7 @@ int plan_balanced_level(Workspace* W, const Request& R, const SortDesc& d, hipSt
   clusters->clear();
   const int ks = key_size_of(R.kind);
   const int64_t n = R.num;
-  if (R.nsegs > 0 || n < kBalancedMinN || ks < 4) return SRS_OK;
+  if (R.nsegs > 0 || n < hook_or(g_first.balanced_min_n, kBalancedMinN) || ks < 4) return SRS_OK;
   const int64_t blocks = std::min<int64_t>(kSampleMaxChunks, n / kSampleChunk);
   const int64_t stride = n / blocks;
   // shist: the 64K-bin histogram, then the workgroups' partial rows
@@ -903,6 +915,7 @@ int run_level(Workspace* W, int ks, const SortDesc* d_desc, LevelState& S, hipSt
     level_keys = W->h_totals[3];
   }
   S.known_len = -1;
+  S.ntiles = ntiles;
   const int lv = ++S.level;
   const double level_elems = (double)level_keys;
   note_elems("count", level_elems, lv);
@@ -1300,10 +1313,13 @@ struct Layout {
 int choose_layout(Workspace* W, const Request& R, Layout* L) {
   const int64_t n = R.num;
   // (the mid-size launch moves the columns as they are: no slices, no pairs)
-  L->mid = R.nsegs == 0 && n > kLocalCap && n <= kMidMaxKeys && mid_enabled();
+  // (srs_debug_set_first_level: from general_min_n records on, a plain start)
+  const int64_t general_min = g_first.general_min_n.load(std::memory_order_relaxed);
+  const bool one_launch = mid_enabled() && !(general_min > 0 && n >= general_min);
+  L->mid = R.nsegs == 0 && n > kLocalCap && n <= kMidMaxKeys && one_launch;
   // (above it, the first level in one launch; the layout is the general path's
   // except C2's interleaved pair words, which that launch's scatter does not write)
-  L->mid1 = R.nsegs == 0 && n > kMidMaxKeys && n <= mid_level_max_n() && mid_enabled();
+  L->mid1 = R.nsegs == 0 && n > kMidMaxKeys && n <= mid_level_max_n() && one_launch;
   const bool general = n > kLocalCap && R.nsegs == 0 && !L->mid;
 
   // AoS records of 16+ bytes travel as SoA slice columns through the
@@ -1354,10 +1370,12 @@ int choose_layout(Workspace* W, const Request& R, Layout* L) {
 // Plans the first level from the key sample and fills the descriptor's table
 // fields: a digit table, a range level (F->one_value: nothing to sort), or
 // neither.
-int plan_first_level(Workspace* W, const Request& R, SortDesc& d, hipStream_t st,
-                     FirstLevel* F) {
+int plan_first_level(Workspace* W, const Request& R, const Layout& L, SortDesc& d,
+                     hipStream_t st, FirstLevel* F) {
   std::vector<KeyCluster> clusters;
-  SRS_TRY(plan_balanced_level(W, R, d, st, F, &clusters));
+  // (the sample's sizes are above the one-launch starts' unless
+  // srs_debug_set_first_level lowers them: those starts take no table)
+  if (!L.mid && !L.mid1) SRS_TRY(plan_balanced_level(W, R, d, st, F, &clusters));
   if (!clusters.empty()) {
     SRS_TRY(plan_range_level(W, R, clusters, d, st, F));
     F->balanced = F->ranges;  // (the range level runs where a digit-table level would)
@@ -1572,13 +1590,17 @@ void start_plain(const SortRun& X, LevelState& S) {
 // The first work lists (the descriptor is written with them), from one of
 // four origins. S.known_len is set where the host knows the single big
 // segment's length: the plain start, and one large caller segment.
-int start_lists(const SortRun& X, const Layout& L, LevelState& S, bool* done) {
+// *start: 0 the plain start or caller segments, 1 the mid-size launch, 2 the
+// mid-level launch.
+int start_lists(const SortRun& X, const Layout& L, LevelState& S, bool* done, int* start) {
   *done = false;
+  *start = 0;
   SRS_TRY(ensure_lists(X.W, 0, 0, 0));
   if (X.R.nsegs > 0) return start_segments(X, S);
   bool started = false;  // (by a one-launch start; else it was refused)
   if (L.mid) SRS_TRY(start_mid_sort(X, S, &started, done));
   if (L.mid1) SRS_TRY(start_mid_level(X, S, &started, done));
+  if (started || *done) *start = L.mid ? 1 : 2;
   if (!started && !*done) start_plain(X, S);
   return SRS_OK;
 }
@@ -1589,23 +1611,35 @@ int start_lists(const SortRun& X, const Layout& L, LevelState& S, bool* done) {
 // second level's scatter, which writes into one bucket's window, measured
 // 5.9 ms per C1 launch against 7.0 for the first one over the whole array),
 // then the gathered level over the buckets. *ran: this sort took them.
-int run_stripe_levels(const SortRun& X, const FirstLevel& F, int ks, LevelState& S, bool* ran) {
+int run_stripe_levels(const SortRun& X, const FirstLevel& F, int ks, bool plain_start,
+                      LevelState& S, bool* ran) {
   Workspace* W = X.W;
   hipStream_t st = X.st;
   const int64_t n = X.R.num;
   const int key_bits = X.d.key_bits;
-  // (a balanced first level: its 512 digit-table groups are the buckets)
-  const int b1 = F.balanced ? kMaxDigitBits : choose_bits(n, key_bits);
-  const int64_t stripe_len = (int64_t)kStripeKeysPerBucket << b1;
+  // (a balanced first level: its 512 digit-table groups are the buckets;
+  // the width and the stripe length may come from srs_debug_set_first_level)
+  const int hook_bits = g_first.first_bits.load(std::memory_order_relaxed);
+  const int b1 = F.balanced ? kMaxDigitBits
+                 : hook_bits > 0 ? std::min(hook_bits, key_bits) : choose_bits(n, key_bits);
+  const int64_t hook_pairs = g_first.stripe_pairs.load(std::memory_order_relaxed);
+  const int64_t stripe_len = hook_pairs > 0 ? hook_pairs * 2 * kTile
+                                            : (int64_t)kStripeKeysPerBucket << b1;
   // Only when the first digit (or the digit table) spreads the keys: a
   // plain level skips a digit all keys share, a stripe level cannot (all-zero
   // keys: 9.4 ms plain, 17.7 ms with stripes), so the key sample decides.
+  // (plain_start: always at the planner's own sizes, which are above the
+  // one-launch starts')
   *ran = X.R.nsegs == 0 && !X.d.canon_zero && (ks == 4 || ks == 8) &&
-         (F.balanced || F.spread) && !F.ranges_final &&
-         n >= kStripeMinN && n < (int64_t(1) << 32) && n >= 2 * stripe_len &&
-         stripes_enabled();
+         (F.balanced || F.spread) && !F.ranges_final && plain_start &&
+         n >= hook_or(g_first.stripe_min_n, kStripeMinN) && n < (int64_t(1) << 32) &&
+         n >= 2 * stripe_len && stripes_enabled();
   if (!*ran) return SRS_OK;
   const int64_t K = (n + stripe_len - 1) / stripe_len;
+  int64_t* info = W->first_level_info;
+  info[2] = 1;
+  info[3] = K;
+  info[4] = b1;
   std::vector<Seg> hs(K);
   for (int64_t k = 0; k < K; k++)
     hs[k] = Seg{k * stripe_len, std::min(stripe_len, n - k * stripe_len), key_bits, X.home};
@@ -1643,7 +1677,9 @@ int run_stripe_levels(const SortRun& X, const FirstLevel& F, int ks, LevelState&
   m2.gt = (const GTile*)W->gtile.p;
   m2.nt_over = (const int32_t*)W->nt_over.p;
   m2.torder = (const int32_t*)W->gorder.p;
-  return run_level(W, X.ksl, X.d_desc, S, st, m2);
+  SRS_TRY(run_level(W, X.ksl, X.d_desc, S, st, m2));
+  info[5] = S.ntiles;
+  return SRS_OK;
 }
 
 int run_sort(Workspace* W, const Request& R, hipStream_t st) {
@@ -1667,7 +1703,11 @@ int run_sort(Workspace* W, const Request& R, hipStream_t st) {
 
   // ---- the first level's plan (key sample: digit table, ranges, stripes) ----
   FirstLevel F;
-  SRS_TRY(plan_first_level(W, R, d, st, &F));
+  SRS_TRY(plan_first_level(W, R, L, d, st, &F));
+  // (srs_debug_last_first_level: the start, the level's kind, the stripes)
+  int64_t* info = W->first_level_info;
+  std::fill(info, info + 6, 0);
+  info[1] = !F.balanced ? 0 : F.ranges ? 2 : F.lut_mode;
   if (F.one_value) return copy_through(R, st);  // (stable: nothing moves)
   SRS_TRY(ensure(W->desc, sizeof(SortDesc)));
   const SortRun X{W, R, d, (SortDesc*)W->desc.p, ksl, inplace ? BUF_OUT : BUF_IN, st};
@@ -1675,14 +1715,16 @@ int run_sort(Workspace* W, const Request& R, hipStream_t st) {
   // ---- the first work lists ---------------------------------------------------
   LevelState T{0, 0, 0, 0, 0, d.ncols, d.tmp2};
   bool done = false;
-  SRS_TRY(start_lists(X, L, T, &done));
+  int start = 0;
+  SRS_TRY(start_lists(X, L, T, &done, &start));
+  info[0] = start;
   if (done) return SRS_OK;
   LevelState S = level_state(d, ks, L.aos_cols, T.nbig, T.n_local, T.n_local2, T.n_copy,
                              T.known_len);
 
   // ---- the levels: stripe pair or table level, then general levels ------------
   bool stripes = false;
-  SRS_TRY(run_stripe_levels(X, F, ks, S, &stripes));
+  SRS_TRY(run_stripe_levels(X, F, ks, start == 0, S, &stripes));
   int level = stripes ? 2 : 0;
   if (F.balanced && !stripes && S.nbig > 0) {
     ++level;
@@ -2818,6 +2860,32 @@ int srs_debug_level_counts(int64_t* counts) {
 
 int srs_debug_set_super_scan(int64_t min_groups) {
   set_super_scan_min_groups(min_groups);
+  return SRS_OK;
+}
+
+int srs_debug_set_first_level(int64_t general_min_n, int64_t balanced_min_n,
+                              int64_t stripe_min_n, int64_t stripe_pairs, int first_bits) {
+  // (the planner's longest stripe: kStripeKeysPerBucket << kMaxDigitBits)
+  constexpr int64_t kMaxPairs = ((int64_t)kStripeKeysPerBucket << kMaxDigitBits) / (2 * kTile);
+  static_assert(kMaxPairs * 2 * kTile == (int64_t)kStripeKeysPerBucket << kMaxDigitBits,
+                "the planner's stripes are whole tile pairs");
+  if (stripe_pairs > kMaxPairs || first_bits > kMaxDigitBits)
+    return fail(SRS_ERR_INVALID_ARG,
+                "srs_debug_set_first_level: stripe_pairs <= 244 and first_bits <= 9");
+  g_first.general_min_n = std::max<int64_t>(general_min_n, 0);
+  g_first.balanced_min_n = std::max<int64_t>(balanced_min_n, 0);
+  g_first.stripe_min_n = std::max<int64_t>(stripe_min_n, 0);
+  g_first.stripe_pairs = std::max<int64_t>(stripe_pairs, 0);
+  g_first.first_bits = std::max(first_bits, 0);
+  return SRS_OK;
+}
+
+int srs_debug_last_first_level(int64_t* out) {
+  if (!out) return fail(SRS_ERR_INVALID_ARG, "out is NULL");
+  Workspace* W = nullptr;
+  WsLock lk;
+  SRS_TRY(acquire_ws(&W, &lk));
+  std::copy(W->first_level_info, W->first_level_info + 6, out);
   return SRS_OK;
 }
 

@@ -132,6 +132,8 @@ struct Workspace {
   std::map<hipStream_t, DevBuf> small_taken;
   bool last_small = false;
   hipStream_t last_small_stream = nullptr;
+  // what the last sort above kLocalCap did first (srs_debug_last_first_level)
+  int64_t first_level_info[6] = {-1, 0, 0, 0, 0, 0};
   // one call at a time per device (calls on different devices run in
   // parallel: the multi-GPU host split sorts its shards from several threads)
   std::mutex mu;
@@ -210,6 +212,7 @@ struct LevelState {
   int pair_tiles = 0;      // the scatter takes two count tiles per workgroup (pair_tiles_mode)
   bool row_offs = false;   // and sums its tile offsets from the count rows (SRS_PAIR_ROW_OFFS)
   int level = 0;           // global levels run so far (per-level timing names)
+  int64_t ntiles = 0;      // tiles of the last level run
 };
 enum TableKind {
   TABLE_NONE = 0,   // a plain digit

@@ -114,6 +114,8 @@ def lib() -> ctypes.CDLL:
                                        ctypes.c_int, vp, i32, vp, vp, vp, vp]
     L.srs_debug_last_fallbacks.argtypes = [ctypes.POINTER(i64)]
     L.srs_debug_set_super_scan.argtypes = [i64]
+    L.srs_debug_set_first_level.argtypes = [i64, i64, i64, i64, ctypes.c_int]
+    L.srs_debug_last_first_level.argtypes = [ctypes.POINTER(i64)]
     L.srs_debug_last_local_counts.argtypes = [ctypes.POINTER(i64)]
     L.srs_debug_last_local_classes.argtypes = [ctypes.POINTER(i64)]
     L.srs_set_host_devices.argtypes = [i32, vp]
@@ -978,6 +980,35 @@ def debug_set_super_scan(min_groups: int) -> None:
     """Scan groups from which a one-segment level takes the super-group
     column scan (srs_debug_set_super_scan; 0 = the default, 256)."""
     _check(lib().srs_debug_set_super_scan(int(min_groups)))
+
+
+def debug_set_first_level(general_min_n: int = 0, balanced_min_n: int = 0, stripe_min_n: int = 0,
+                          stripe_pairs: int = 0, first_bits: int = 0) -> None:
+    """The first level's size rules, process-wide (srs_debug_set_first_level):
+    records from which a sort starts plain, takes the key sample, takes the
+    stripe level; the stripe length in tile pairs of 8192 records; the plain
+    stripe level's digit width. 0 (or less) is a field's default: called
+    without arguments it restores every default, which a test does in a
+    `finally` or a fixture."""
+    _check(lib().srs_debug_set_first_level(int(general_min_n), int(balanced_min_n),
+                                           int(stripe_min_n), int(stripe_pairs),
+                                           int(first_bits)))
+
+
+FIRST_LEVEL_FIELDS = ("start", "kind", "stripes", "stripe_count", "first_bits", "gathered_tiles")
+START_PLAIN, START_MID, START_MID_LEVEL = 0, 1, 2
+LEVEL_PLAIN, LEVEL_TABLE16, LEVEL_RANGES, LEVEL_SPLIT_TABLE = 0, 1, 2, 3
+
+
+def debug_last_first_level() -> dict:
+    """What the last sort above the single-workgroup capacity did on the
+    current device (srs_debug_last_first_level), by FIRST_LEVEL_FIELDS: its
+    start (START_*; -1: no such sort yet), the first level's kind (LEVEL_*),
+    whether the stripe and gathered levels ran, the stripe count, the stripe
+    level's digit width, the gathered level's tile count."""
+    c = (ctypes.c_int64 * 6)()
+    _check(lib().srs_debug_last_first_level(c))
+    return dict(zip(FIRST_LEVEL_FIELDS, (int(x) for x in c)))
 
 
 def debug_set_topk_candidates(max_candidates: int) -> None:

@@ -85,6 +85,33 @@ def test_argument_validation_without_gpu():
     assert b"aligned" in lib.srs_last_error()
 
 
+def test_first_level_hook_without_gpu():
+    """srs_debug_set_first_level validates its arguments and restores its
+    defaults without touching a device; srs_debug_last_first_level answers
+    with a code (the report, or the device error where there is no GPU)."""
+    import srs_amd
+    lib = srs_amd.lib()
+    try:
+        assert lib.srs_debug_set_first_level(1, 1, 1, 1, 8) == 0
+        assert lib.srs_debug_set_first_level(1 << 40, 1 << 40, 1 << 40, 244, 9) == 0
+        assert lib.srs_debug_set_first_level(0, 0, 0, 245, 0) == -1
+        assert b"stripe_pairs" in lib.srs_last_error()
+        assert lib.srs_debug_set_first_level(0, 0, 0, 0, 10) == -1
+        assert lib.srs_debug_set_first_level(-5, -5, -5, -5, -5) == 0  # (<= 0: the defaults)
+        with pytest.raises(srs_amd.SrsError):
+            srs_amd.debug_set_first_level(stripe_pairs=1 << 20)
+    finally:
+        srs_amd.debug_set_first_level()
+    assert lib.srs_debug_last_first_level(None) == -1
+    out = (ctypes.c_int64 * 6)(*[7] * 6)
+    rc = lib.srs_debug_last_first_level(out)
+    if rc == 0:  # (a GPU is present: -1 unless a sort has run in this process)
+        assert out[0] in (-1, 0, 1, 2) and 7 not in list(out)
+    else:  # no device to look the workspace up on: SRS_ERR_HIP, from hipGetDevice
+        assert rc == -3 and b"hipGetDevice" in lib.srs_last_error()
+        assert list(out) == [7] * 6
+
+
 def _kernel_resources():
     """Per-kernel VGPRs / scratch / occupancy from the build's compiler
     remarks (simd-radix-sort_amd/build/srs_kernels.remarks)."""
